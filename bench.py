@@ -16,6 +16,12 @@ RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or plain
 `python bench.py --gpus N`: with no WORLD_SIZE in the environment the process becomes a
 launcher that never touches the GPU, starts the N ranks as child processes, relays rank 0's
 line and exits with the worst exit code (launch_ranks).  Prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, warm up, time --steps steps, write the
+outputs of the last timed step if --dump-outputs is given, print the line.  --full adds what is
+measured beside the headline: the CPU baseline, the box's stream rates, the step with the
+constant-line shortcut, the kernel table of the slab engine (extra steps behind the timed
+region) and the --iir-fma comparison with the oracle.
 """
 import argparse
 import importlib
@@ -76,6 +82,9 @@ def kernel_alg_bytes(args):
 SIMDS, SUSTAINED_GHZ = 1024, 2.03  # GRBM_GUI_ACTIVE / 8 / duration under this load
 PROFILE_JSON = "r03_traffic.json"
 
+# --dump-outputs: at most this many bytes of features, drawn at voxels fixed by DUMP_SEED
+DUMP_BYTES, DUMP_SEED = 32 << 20, 0x1FE0D0
+
 
 def parse():
     ap = argparse.ArgumentParser()
@@ -97,8 +106,8 @@ def parse():
     ap.add_argument("--iir-ckpt", type=int, default=None)
     ap.add_argument("--iir-fma", action="store_true",
                     help="the RELAXED line, never the headline: fused multiply-adds in the line "
-                         "recurrences (IFE_OPT_IIR_FMA, not the reference's arithmetic).  The run then "
-                         "also compares the whole output with the oracle at full size and prints the "
+                         "recurrences (IFE_OPT_IIR_FMA, not the reference's arithmetic).  With --full the "
+                         "run also compares the whole output with the oracle at full size and prints the "
                          "MAXIMUM eigenvalue error (config.iir_fma = 1, `relaxed` in the JSON line)")
     ap.add_argument("--relaxed-bar", type=float, default=None,
                     help="--iir-fma: fail if the maximum eigenvalue error / |lambda1| exceeds this")
@@ -140,7 +149,18 @@ def parse():
                          "sum and rank 0 prints a stub line (tests/test_bench_launch.py)")
     ap.add_argument("--launch-timeout", type=float, default=900.0,
                     help="self-launch: seconds after which the launcher ends its ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beside the headline (CPU baseline, stream probe, "
+                         "constant-line shortcut, slab kernel table, --iir-fma comparison); the "
+                         "--no-* options above leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/features.npy: "
+                         "float32 [scale, voxel, feature] in interleaved order, at every voxel when the "
+                         "output fits in %d MiB, else at a fixed seeded sample of voxels (dump_voxels)"
+                    % (DUMP_BYTES >> 20))
     a = ap.parse_args()
+    if a.relaxed_bar is not None and not (a.full and a.iir_fma):
+        ap.error("--relaxed-bar needs --iir-fma --full (the comparison with the oracle)")
     if a.proxy_world:
         if a.gpus != 1 or not 0 <= a.proxy_rank < a.proxy_world:
             ap.error("--proxy-world needs --gpus 1 and 0 <= --proxy-rank < --proxy-world")
@@ -310,6 +330,55 @@ def measured_stream_gbs(torch, ctx, dev, nbytes=4 << 30, reps=5):
     return fill, copy
 
 
+def dump_voxels(nvox, n_scales):
+    """Flat voxel indices (z, y, x order) whose features --dump-outputs writes: every voxel when
+    the whole output fits in DUMP_BYTES, else a sorted seeded draw, the same for every build."""
+    m = DUMP_BYTES // (n_scales * 8 * 4)
+    if nvox <= m:
+        return np.arange(nvox, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, nvox, m, dtype=np.int64))
+
+
+def local_features(torch, d_out, layout_planar, n_scales, idx):
+    """d_out[scale, voxel, feature] at the flat voxel indices idx of this output (a device
+    tensor), whichever layout the step wrote."""
+    if layout_planar:  # [scale][feature][voxel]
+        return d_out.reshape(n_scales, 8, -1).index_select(2, idx).transpose(1, 2)
+    return d_out.reshape(n_scales, -1, 8).index_select(1, idx)
+
+
+def dump_outputs(torch, dist, runner, args, use_dist, rank, world, dev):
+    """What the last timed step left in the output volumes, at dump_voxels(), written by rank 0 to
+    DIR/features.npy.  Slab engine: each rank reads the voxels of its own slab and rank 0
+    assembles them in order, so that N ranks write what one device does (a --proxy-world run:
+    the voxels of its one slab)."""
+    nz, ny, nx = args.size
+    n_scales, plane = len(args.sigmas), ny * nx
+    idx = dump_voxels(nz * plane, n_scales)
+    planar = args.layout == "planar"
+    if not use_dist:
+        feats = local_features(torch, runner.d_out, planar, n_scales, torch.from_numpy(idx).to(dev)).cpu().numpy()
+    else:
+        slab = importlib.import_module(PKG + ".slab")
+        srank, sworld = (args.proxy_rank, args.proxy_world) if args.proxy_world else (rank, world)
+        bounds = slab.slab_bounds(nz, sworld)
+        owner = np.searchsorted(bounds, idx // plane, side="right") - 1  # slabs are z ranges
+        mine = idx[owner == srank] - bounds[srank] * plane
+        local = local_features(torch, runner.d_out, planar, n_scales, torch.from_numpy(mine).to(dev))
+        if world == 1:
+            feats = local.cpu().numpy()
+        else:  # idx is sorted, so rank r's voxels are one run of it: gather equal-sized parts
+            part = torch.zeros((n_scales, len(idx), 8), dtype=torch.float32, device=dev)
+            part[:, :len(mine)] = local
+            parts = [torch.empty_like(part) for _ in range(world)]
+            dist.all_gather(parts, part)
+            feats = np.concatenate([parts[r][:, :int((owner == r).sum())].cpu().numpy()
+                                    for r in range(world)], axis=1)
+    if rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "features.npy"), np.ascontiguousarray(feats, np.float32))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -364,7 +433,7 @@ def main():
     # launches of 0.3-2 ms per step, the records cost nothing measurable (8.86 vs 8.88 ms).  Slab
     # engine: ~26 launches of 20-60 us per step on two streams, where the records cost 2.7 % of
     # the step (scripts/experiments/r3_events_cost.sh: 1.367 -> 1.330 ms); there the K timed
-    # steps run without them and the kernel table comes from extra steps behind the timed region.
+    # steps run without them and the kernel table (--full) comes from extra steps behind the timed region.
     events_in_timed = not use_dist and not args.no_kernel_events
     for c in runner.contexts():
         c.set_option(pkg.OPT_PROFILE, 1 if events_in_timed else 0)
@@ -377,8 +446,10 @@ def main():
     torch.cuda.synchronize()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(torch, dist, runner, args, use_dist, rank, world, dev)
     ksteps = args.steps  # steps the kernel table below is summed over
-    if use_dist and not args.no_kernel_events:
+    if use_dist and not args.no_kernel_events and args.full:
         ksteps = min(args.steps, 5)
         for c in runner.contexts():
             c.set_option(pkg.OPT_PROFILE, 1)
@@ -395,7 +466,7 @@ def main():
         c.set_option(pkg.OPT_PROFILE, 0)
     # beside the headline: the same step with the library's default constant-line shortcut
     shortcut_ms = None
-    if not use_dist and not args.const_lines and not args.no_shortcut_leg:
+    if args.full and not use_dist and not args.const_lines and not args.no_shortcut_leg:
         runner.ctx.set_option(pkg.OPT_CONST_LINES, 1)
         runner.step()
         torch.cuda.synchronize()
@@ -406,10 +477,10 @@ def main():
         shortcut_ms = (time.perf_counter() - t1) / 3 * 1e3
         runner.ctx.set_option(pkg.OPT_CONST_LINES, 0)
     relaxed = None
-    if args.iir_fma and not use_dist:
+    if args.full and args.iir_fma and not use_dist:
         relaxed = relaxed_error(runner, synth, seed, sigmas, args)
     fill_gbs = copy_gbs = None
-    if rank == 0 and not use_dist and not args.no_stream_probe:
+    if args.full and rank == 0 and not use_dist and not args.no_stream_probe:
         runner.release_outputs()  # the output volumes go back to the allocator before the probe's 8 GiB
         fill_gbs, copy_gbs = measured_stream_gbs(torch, runner.ctx, dev)
 
@@ -486,7 +557,9 @@ def main():
                 "scope": ("this rank's share of one step over the step's wall time (%.3f ms; the kernels "
                           "of its two streams overlap: their hipEvent durations, taken over %d extra steps "
                           "behind the timed region, sum to %.3f ms); "
-                          % (scope_ms, ksteps, dev_ms_step) if use_dist else
+                          % (scope_ms, ksteps, dev_ms_step) if use_dist and kern else
+                          "this rank's share of one step over the step's wall time (%.3f ms; kernel "
+                          "table: --full); " % scope_ms if use_dist else
                           "all kernels of one step (sum of hipEvent durations %.3f ms); " % dev_ms_step)
                          + "algorithmic bytes = 37 B x voxels x scales",
                 "dominant_kernel": dominant, "kernels": kern}
@@ -524,6 +597,7 @@ def main():
     }
     if relaxed is not None:
         out["relaxed"] = relaxed
+    if args.iir_fma:
         out["headline"] = False
     if args.proxy_world:
         out["headline"] = False
@@ -532,7 +606,7 @@ def main():
                                   "step, an upper bound on what %d such GPUs could reach"
                                   % (args.proxy_rank, args.proxy_world, args.proxy_world))
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(synth, seed, sigmas, args.cpu_sample)
         print(json.dumps(out), flush=True)
     if use_dist:
