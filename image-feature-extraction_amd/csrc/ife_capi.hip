@@ -1280,8 +1280,19 @@ int ife_emphysema_features_begin(ife_ctx *ctx, const void *image, int image_dtyp
   if (!ctx->sc_copy) IFE_HIP(ctx, hipStreamCreateWithFlags(&ctx->sc_copy, hipStreamNonBlocking));
   const void *dI, *dM;
   if ((rc = stage_in(ctx, IFE_MEM_HOST, image, n * dtype_size(image_dtype), ctx->st_img, &dI))) return rc;
-  if ((rc = stage_in(ctx, IFE_MEM_HOST, mask, n * (mask ? dtype_size(mask_dtype) : 0), ctx->st_mask, &dM)))
+  if ((rc = stage_in(ctx, IFE_MEM_HOST, mask, n * (mask ? dtype_size(mask_dtype) : 0), ctx->st_mask, &dM))) {
+    (void)hipStreamSynchronize(ctx->stream);  // the image upload may still read the caller's memory
     return rc;
+  }
+  // From page-locked memory the uploads run asynchronously to the host: the caller may reuse
+  // image and mask once _begin returns, so it waits for them (not for the scales) before returning.
+  hipEvent_t uploaded = nullptr;
+  if (hipEventCreateWithFlags(&uploaded, hipEventDisableTiming) != hipSuccess ||
+      hipEventRecord(uploaded, ctx->stream) != hipSuccess) {
+    if (uploaded) (void)hipEventDestroy(uploaded);
+    (void)hipStreamSynchronize(ctx->stream);
+    return fail(ctx, IFE_E_HIP, "upload event: %s", hipGetErrorString(hipGetLastError()));
+  }
   float *dout = (float *)ctx->sc_out.p;
   const bool u16 = mask && mask_dtype == IFE_U16;
   ctx->scale_events = &ctx->sc_done;
@@ -1292,6 +1303,9 @@ int ife_emphysema_features_begin(ife_ctx *ctx, const void *image, int image_dtyp
     rc = u16 ? emphysema_typed(ctx, (const int16_t *)dI, (const uint16_t *)dM, vol, sigmas, n_sigmas, dout, layout)
              : emphysema_typed(ctx, (const int16_t *)dI, (const uint8_t *)dM, vol, sigmas, n_sigmas, dout, layout);
   ctx->scale_events = nullptr;
+  const hipError_t up = hipEventSynchronize(uploaded);
+  (void)hipEventDestroy(uploaded);
+  if (!rc && up != hipSuccess) rc = fail(ctx, IFE_E_HIP, "upload: %s", hipGetErrorString(up));
   if (rc) (void)ife_emphysema_features_end(ctx);
   return rc;
 }

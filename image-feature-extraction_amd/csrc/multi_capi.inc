@@ -29,6 +29,7 @@ struct MultiRank {
   std::vector<DevBuf> zo, xo, pad, ck;        // [scale * nf + field]
   std::vector<DevBuf> c_in, c_out, a_in, a_out;  // [item]
   std::vector<hipEvent_t> ev;                  // every event of a run, destroyed at its end
+  hipEvent_t uploaded = nullptr;               // behind the run's uploads from host memory (one of ev)
 };
 
 }  // namespace
@@ -110,6 +111,7 @@ void mfree_rank(MultiRank &R) {
   if (R.sd) (void)hipStreamSynchronize(R.sd);
   for (auto e : R.ev) (void)hipEventDestroy(e);
   R.ev.clear();
+  R.uploaded = nullptr;
   std::vector<DevBuf *> bufs = {&R.img, &R.mask, &R.src[0], &R.src[1], &R.out};
   for (auto *v : {&R.zo, &R.xo, &R.pad, &R.ck, &R.c_in, &R.c_out, &R.a_in, &R.a_out})
     for (auto &b : *v) bufs.push_back(&b);
@@ -302,6 +304,7 @@ int multi_run(ife_multi *m, const void *image, int image_dtype, const void *mask
     if (mask)
       IFE_MHIP(m, hipMemcpyAsync(R.mask.p, (const char *)mask + (size_t)((R.z0 - R.lo) * plane) * msz, nve * msz,
                                  hipMemcpyHostToDevice, R.sb));
+    if ((rc = mrecord(m, R, R.sb, &R.uploaded))) return rc;
   }
 
   // ---- prepare, then the two state chains in wavefront order -----------------------------
@@ -492,6 +495,7 @@ int multi_drain(ife_multi *m, bool failed) {
       result = mfail(m, IFE_E_HIP, "device %d: synchronisation failed: %s", R.dev, hipGetErrorString(e));
     for (auto ev : R.ev) (void)hipEventDestroy(ev);
     R.ev.clear();
+    R.uploaded = nullptr;
   }
   (void)hipGetLastError();
   return result;
@@ -518,14 +522,21 @@ int ife_multi_emphysema_features(ife_multi *m, const void *image, int image_dtyp
 // to the host: _begin uploads the slabs once, runs the prepass once and enqueues EVERY scale on
 // every device (nothing is waited for); _fetch(k) blocks until scale k of every slab has been
 // copied into `out` (the whole volume of that scale, host memory) while the later scales keep
-// computing; _end drains.  The inputs must stay valid until _begin returns (the uploads are
-// synchronous with respect to pageable host memory), `out` until its _fetch returns.
+// computing; _end drains.  The inputs may be reused once _begin returns: it waits for the uploads
+// (from page-locked memory they run asynchronously to the host), not for the scales; `out` must
+// stay valid until its _fetch returns.
 int ife_multi_emphysema_features_begin(ife_multi *m, const void *image, int image_dtype, const void *mask,
                                        int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
                                        int n_sigmas, int layout) {
   if (!m) return IFE_E_ARG;
   if (m->streaming) return mfail(m, IFE_E_STATE, "a streaming call is already in flight");
-  const int rc = multi_run(m, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout);
+  int rc = multi_run(m, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout);
+  for (auto &R : m->ranks) {  // the caller may reuse image and mask from here on
+    if (rc != IFE_OK) break;
+    hipError_t e = hipSetDevice(R.dev);
+    if (e == hipSuccess && R.uploaded) e = hipEventSynchronize(R.uploaded);
+    if (e != hipSuccess) rc = mfail(m, IFE_E_HIP, "device %d: upload: %s", R.dev, hipGetErrorString(e));
+  }
   if (rc != IFE_OK) {
     (void)multi_drain(m, true);
     return rc;

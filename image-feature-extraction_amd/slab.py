@@ -439,12 +439,22 @@ class SlabEngine:
         n = len(self.items)
         self.sent = [[None] * n, [None] * n]      # pending sends of the previous step
         self.consumed = [[None] * n, [None] * n]  # events: in-state read by its sweep
+        self.inputs_read = None   # event (bulk stream): the last step's readers of img_slab / mask_slab have run
 
     # ---- one step -------------------------------------------------------------------
-    def run(self, img_slab, mask_slab, out):
+    def run(self, img_slab, mask_slab, out, ready=None):
         """img_slab [pad_lo + nzl + pad_hi][ny][nx] f32|i16: the rank's planes of the raw volume
         with the overlap of `overlap(rank, world)`; mask_slab the same planes, u8|u16, or None;
-        out [S][nzl][ny][nx][8] (or [S][8][nzl][ny][nx] planar) float32: the rank's own planes."""
+        out [S][nzl][ny][nx][8] (or [S][8][nzl][ny][nx] planar) float32: the rank's own planes.
+
+        Input contract (GPU): the prepass reads img_slab and mask_slab on the CHAIN stream, which
+        is not ordered after the caller's stream -- it may start while the bulk work of earlier
+        steps is still queued.  A caller that writes the inputs on the device before a step passes
+        `ready`, an event recorded after those writes; the chain and the bulk stream wait for it
+        before they read.  After run() returns, `inputs_read` is an event on the bulk stream behind
+        every reader of this step's inputs (the prepass, and the feature pass that reads the mask);
+        the inputs must not be overwritten before it.  Inputs that do not change between steps
+        need neither."""
         if img_slab.shape[0] != self.pad_lo + self.nzl + self.pad_hi:
             raise ValueError("the slab of rank %d needs %d + %d + %d planes (overlap below, own, above), got %d"
                              % (self.rank, self.pad_lo, self.nzl, self.pad_hi, img_slab.shape[0]))
@@ -479,6 +489,7 @@ class SlabEngine:
             # this set was last used `depth` steps ago: its fused sweeps have read src and ck
             # (its lean sweeps stand earlier in this very stream)
             wait(chain, self.fdone[par])
+            wait(chain, ready)   # the caller's writes of the inputs
             st.prepare(img_slab, mask_slab if self.has_mask else None, src[0],
                        src[1] if self.has_mask else None)
         wait(fstream, self.free[par])  # ... and its X pass has read the Z output
@@ -523,6 +534,7 @@ class SlabEngine:
 
         first = 0 if has_lo else 1
         fat = 1 - self.lean
+        wait(bulk, ready)  # the feature pass reads the mask
         for qs in self.bulk_groups:
             ss = [s for q in qs for s in self.scale_groups[q]]
             for i, (qi, g) in enumerate(self.items):
@@ -547,6 +559,8 @@ class SlabEngine:
                             mask_slab[self.pad_lo:self.pad_lo + self.nzl] if self.has_mask else None,
                             slab_shape, sp,
                             1 if has_lo else 0, 1 if has_hi else 0, out[s], self.layout)
+        # bulk waited for every fused sweep, and those for the lean sweeps behind the prepass
+        self.inputs_read = rec(bulk)
 
     def finish(self):
         """Wait for the sends of the last step (call before tearing the process group down)."""

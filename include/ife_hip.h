@@ -211,7 +211,9 @@ int ife_emphysema_features(ife_ctx *ctx, const void *image, int image_dtype, con
  * stream of its own -- so a caller can write scale k to disk while the device is still busy
  * with the later scales, and never holds more than one scale in host memory; _end frees the
  * device copy (also done by the next _begin and by ife_ctx_destroy).  IFE_E_STATE when a
- * scale is fetched that _begin did not start. */
+ * scale is fetched that _begin did not start.  _begin returns once image and mask have been
+ * copied to the device (the scales are still running): the caller may overwrite or free them
+ * from then on, page-locked memory included; `out` must stay valid until its _fetch returns. */
 int ife_emphysema_features_begin(ife_ctx *ctx, const void *image, int image_dtype,
                                  const void *mask, int mask_dtype, const ife_volume_desc *vol,
                                  const float *sigmas, int n_sigmas, int layout);
@@ -354,7 +356,8 @@ int ife_multi_emphysema_features(ife_multi *m, const void *image, int image_dtyp
  * _begin uploads every slab once, runs Cast + Multiply once and enqueues every scale on every
  * device without waiting; _fetch(k) blocks until scale k of every slab has been copied into
  * `out` (that scale's whole volume: nx*ny*nz*8 floats of host memory) on a stream of its own,
- * while the later scales keep computing; _end drains.  IFE_E_STATE out of sequence. */
+ * while the later scales keep computing; _end drains.  IFE_E_STATE out of sequence.  As with
+ * ife_emphysema_features_begin, image and mask may be reused as soon as _begin returns. */
 int ife_multi_emphysema_features_begin(ife_multi *m, const void *image, int image_dtype,
                                        const void *mask, int mask_dtype, const ife_volume_desc *vol,
                                        const float *sigmas, int n_sigmas, int layout);

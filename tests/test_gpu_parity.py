@@ -250,6 +250,54 @@ def test_emphysema_stream_equals_one_call(ctx, ife, synth):
     assert rc == ife.E_STATE
 
 
+def _page_locked(a):
+    """A numpy view of a page-locked (pinned) copy of `a`: the uploads from it run
+    asynchronously to the host."""
+    import torch
+    t = torch.from_numpy(a.view({2: np.int16, 4: np.float32, 1: np.uint8}[a.itemsize])).pin_memory()
+    assert t.is_pinned()
+    return t, t.numpy().view(a.dtype)
+
+
+def _overwrite_back_to_front(dst, src):
+    """The planes last in the upload order first, so that a copy still in flight would read them."""
+    for z in range(dst.shape[0] - 1, -1, -1):
+        dst[z] = src[z]
+
+
+def test_emphysema_begin_inputs_reusable_once_it_returns(ife, synth):
+    """ife_emphysema_features_begin from page-locked memory, image and mask overwritten with
+    another volume as soon as it returns (mask first: it is uploaded last), every scale
+    fetched: bit-identical to the blocking call on the original volume.  _begin must not
+    return before its uploads have landed (include/ife_hip.h)."""
+    import ctypes as C
+    shape, spacing, sig = (128, 384, 384), (1.0, 1.0, 1.0), [1.0, 2.0]
+    img = synth.volume_f32(shape, 23)
+    mask = np.minimum(synth.mask_ellipsoids(shape), 1).astype(np.uint8)
+    with ife.Context(0) as c:
+        c.set_option(ife.OPT_TRIG_MODE, 0)
+        want = c.emphysema_features(img, mask, sig, spacing)
+        keep_i, p_img = _page_locked(img)
+        keep_m, p_mask = _page_locked(mask)
+        other_img = synth.volume_f32(shape, 24)
+        other_mask = (synth.volume_f32(shape, 25) > 300).astype(np.uint8)
+        d = ife._desc(shape, spacing)
+        sigs = (C.c_float * len(sig))(*sig)
+        rc = c._lib.ife_emphysema_features_begin(c._h, p_img.ctypes.data, ife.F32, p_mask.ctypes.data, ife.U8,
+                                                  C.byref(d), sigs, len(sig), ife.INTERLEAVED)
+        assert rc == ife.OK, c._lib.ife_last_error(c._h)
+        _overwrite_back_to_front(p_mask, other_mask)
+        _overwrite_back_to_front(p_img, other_img)
+        try:
+            for k in range(len(sig)):
+                out = np.empty(shape + (8,), np.float32)
+                assert c._lib.ife_emphysema_features_fetch(c._h, k, out.ctypes.data) == ife.OK
+                assert np.array_equal(out.view(np.uint32), want[k].view(np.uint32)), \
+                    "scale %d differs: _begin returned before its uploads had landed" % k
+        finally:
+            assert c._lib.ife_emphysema_features_end(c._h) == ife.OK
+
+
 def test_emphysema_null_mask_equals_ones_mask(ctx, synth):
     shape = (24, 28, 32)
     img = synth.volume_f32(shape, 11)

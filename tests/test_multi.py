@@ -75,3 +75,39 @@ def test_multi_device_streaming_equals_one_call(ife, synth):
         c.set_option(ife.OPT_TRIG_MODE, 0)
         ref = c.emphysema_features(img, mask, sigmas, spacing)
     np.testing.assert_array_equal(want.view(np.uint32), ref.view(np.uint32))
+
+
+def test_multi_device_begin_inputs_reusable_once_it_returns(ife, synth):
+    """ife_multi_emphysema_features_begin from page-locked memory, image and mask overwritten
+    with another volume as soon as it returns (mask first, back to front: the last uploads), every
+    scale fetched: bit-identical to the blocking call on the original volume."""
+    import ctypes as C
+    import torch
+    shape, spacing, sig = (128, 320, 384), (0.7, 0.7, 1.0), [1.0, 2.5]
+    img = synth.volume_i16(shape, 31)
+    mask = np.minimum(synth.mask_ellipsoids(shape), 1).astype(np.uint16)
+    other_img = synth.volume_i16(shape, 32)
+    other_mask = (synth.volume_f32(shape, 33) > 300).astype(np.uint16)
+    t_img = torch.from_numpy(img).pin_memory()
+    t_mask = torch.from_numpy(mask.view(np.int16)).pin_memory()
+    assert t_img.is_pinned() and t_mask.is_pinned()
+    p_img, p_mask = t_img.numpy(), t_mask.numpy().view(np.uint16)
+    with ife.Multi([0, 0, 0]) as m:
+        m.set_option(ife.OPT_TRIG_MODE, 0)
+        want = m.emphysema_features(img, mask, sig, spacing)
+        d = ife._desc(shape, spacing)
+        sigs = (C.c_float * len(sig))(*sig)
+        rc = m._lib.ife_multi_emphysema_features_begin(m._h, p_img.ctypes.data, ife.I16, p_mask.ctypes.data,
+                                                       ife.U16, C.byref(d), sigs, len(sig), ife.INTERLEAVED)
+        assert rc == ife.OK, m._lib.ife_multi_last_error(m._h)
+        for dst, src in ((p_mask, other_mask), (p_img, other_img)):
+            for z in range(shape[0] - 1, -1, -1):
+                dst[z] = src[z]
+        try:
+            for k in range(len(sig)):
+                out = np.empty(shape + (8,), np.float32)
+                assert m._lib.ife_multi_emphysema_features_fetch(m._h, k, out.ctypes.data) == ife.OK
+                assert np.array_equal(out.view(np.uint32), want[k].view(np.uint32)), \
+                    "scale %d differs: _begin returned before its uploads had landed" % k
+        finally:
+            assert m._lib.ife_multi_emphysema_features_end(m._h) == ife.OK
