@@ -181,6 +181,38 @@ _IMG_DT = {np.dtype(np.float32): F32, np.dtype(np.int16): I16}
 _MSK_DT = {np.dtype(np.uint8): U8, np.dtype(np.uint16): U16}
 
 
+def _image_arg(image):
+    """The image as a contiguous array of a dtype the library reads (anything else as float32),
+    and its dtype code."""
+    image = np.ascontiguousarray(image)
+    if image.dtype not in _IMG_DT:
+        image = image.astype(np.float32)
+    return image, _IMG_DT[image.dtype]
+
+
+def _mask_arg(mask):
+    """(contiguous mask, dtype code, pointer); (None, U8, None) without a mask.  The caller keeps
+    the array alive across the call."""
+    if mask is None:
+        return None, U8, None
+    mask = np.ascontiguousarray(mask)
+    if mask.dtype not in _MSK_DT:
+        raise TypeError("mask must be uint8 or uint16")
+    return mask, _MSK_DT[mask.dtype], mask.ctypes.data
+
+
+def _sigma_arg(sigmas):
+    return (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
+
+
+def _ptr_array(ptrs):
+    return (C.c_void_p * len(ptrs))(*ptrs)
+
+
+def _double_array(values):
+    return (C.c_double * len(values))(*[float(v) for v in values])
+
+
 class Context:
     """One ``ife_ctx``: a device, a stream, a workspace.  Single-owner."""
 
@@ -303,38 +335,26 @@ class Context:
     def emphysema_features(self, image, mask, sigmas, spacing=(1.0, 1.0, 1.0),
                            layout=INTERLEAVED):
         """One 8-component volume per sigma: shape (S, nz, ny, nx, 8) or (S, 8, nz, ny, nx)."""
-        image = np.ascontiguousarray(image)
-        if image.dtype not in _IMG_DT:
-            image = image.astype(np.float32)
-        mdt, mptr = U8, None
-        if mask is not None:
-            mask = np.ascontiguousarray(mask)
-            if mask.dtype not in _MSK_DT:
-                raise TypeError("mask must be uint8 or uint16")
-            mdt, mptr = _MSK_DT[mask.dtype], mask.ctypes.data
+        image, idt = _image_arg(image)
+        mask, mdt, mptr = _mask_arg(mask)
         d = _desc(image.shape, spacing)
-        sig = (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
+        sig = _sigma_arg(sigmas)
         shp = image.shape + (8,) if layout == INTERLEAVED else (8,) + image.shape
         out = np.empty((len(sigmas),) + shp, np.float32)
         self._chk(self._lib.ife_emphysema_features(
-            self._h, image.ctypes.data, _IMG_DT[image.dtype], mptr, mdt, C.byref(d), sig,
+            self._h, image.ctypes.data, idt, mptr, mdt, C.byref(d), sig,
             len(sigmas), out.ctypes.data, layout, MEM_HOST))
         return out
 
     def emphysema_features_stream(self, image, mask, sigmas, spacing=(1.0, 1.0, 1.0),
                                   layout=INTERLEAVED):
         """Generator over the scales: begin once, yield one 8-component volume per sigma."""
-        image = np.ascontiguousarray(image)
-        if image.dtype not in _IMG_DT:
-            image = image.astype(np.float32)
-        mdt, mptr = U8, None
-        if mask is not None:
-            mask = np.ascontiguousarray(mask)
-            mdt, mptr = _MSK_DT[mask.dtype], mask.ctypes.data
+        image, idt = _image_arg(image)
+        mask, mdt, mptr = _mask_arg(mask)
         d = _desc(image.shape, spacing)
-        sig = (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
+        sig = _sigma_arg(sigmas)
         self._chk(self._lib.ife_emphysema_features_begin(
-            self._h, image.ctypes.data, _IMG_DT[image.dtype], mptr, mdt, C.byref(d), sig,
+            self._h, image.ctypes.data, idt, mptr, mdt, C.byref(d), sig,
             len(sigmas), layout))
         try:
             shp = image.shape + (8,) if layout == INTERLEAVED else (8,) + image.shape
@@ -346,20 +366,13 @@ class Context:
             self._chk(self._lib.ife_emphysema_features_end(self._h))
 
     def fd_hessian_features(self, image, mask=None, spacing=(1.0, 1.0, 1.0), layout=INTERLEAVED):
-        image = np.ascontiguousarray(image)
-        if image.dtype not in _IMG_DT:
-            image = image.astype(np.float32)
-        mdt, mptr = U8, None
-        if mask is not None:
-            mask = np.ascontiguousarray(mask)
-            if mask.dtype not in _MSK_DT:
-                raise TypeError("mask must be uint8 or uint16")
-            mdt, mptr = _MSK_DT[mask.dtype], mask.ctypes.data
+        image, idt = _image_arg(image)
+        mask, mdt, mptr = _mask_arg(mask)
         d = _desc(image.shape, spacing)
         out = np.empty(image.shape + (6,) if layout == INTERLEAVED else (6,) + image.shape,
                        np.float32)
         self._chk(self._lib.ife_fd_hessian_features(
-            self._h, image.ctypes.data, _IMG_DT[image.dtype], mptr, mdt, C.byref(d),
+            self._h, image.ctypes.data, idt, mptr, mdt, C.byref(d),
             out.ctypes.data, layout, MEM_HOST))
         return out
 
@@ -388,7 +401,7 @@ class Context:
     def emphysema_features_device(self, image_ptr, image_dtype, mask_ptr, mask_dtype, shape_zyx,
                                   spacing, sigmas, out_ptr, layout=INTERLEAVED):
         d = _desc(shape_zyx, spacing)
-        sig = (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
+        sig = _sigma_arg(sigmas)
         self._chk(self._lib.ife_emphysema_features(
             self._h, C.c_void_p(image_ptr), image_dtype, C.c_void_p(mask_ptr or 0), mask_dtype,
             C.byref(d), sig, len(sigmas), C.c_void_p(out_ptr), layout, MEM_DEVICE))
@@ -417,13 +430,10 @@ class Context:
     def stage_recursive_gaussian_batch(self, in_ptrs, out_ptrs, shape_zyx, spacing, axis_xyz,
                                        sigmas, in_y_chunks=1):
         """One launch over len(in_ptrs) float volumes of the same shape (<= 8 jobs)."""
-        n = len(in_ptrs)
         d = _desc(shape_zyx, spacing)
-        ins = (C.c_void_p * n)(*in_ptrs)
-        outs = (C.c_void_p * n)(*out_ptrs)
-        sg = (C.c_double * n)(*[float(s) for s in sigmas])
         self._chk(self._lib.ife_stage_recursive_gaussian_batch(
-            self._h, n, ins, outs, C.byref(d), int(axis_xyz), sg, int(in_y_chunks)))
+            self._h, len(in_ptrs), _ptr_array(in_ptrs), _ptr_array(out_ptrs), C.byref(d), int(axis_xyz),
+            _double_array(sigmas), int(in_y_chunks)))
 
     def stage_features(self, num_ptr, den_ptr, mask_ptr, mask_dtype, slab_shape_zyx, spacing,
                        halo_lo, halo_hi, out_ptr, layout=INTERLEAVED):
@@ -440,52 +450,35 @@ class Context:
     def stage_z_sweep(self, direction, in_ptrs, slab_shape_zyx, spacing, line0, nlines, sigmas,
                       has_neighbour, state_in_ptr, state_out_ptr, ck_ptrs):
         """Causal (direction 0) or anticausal (1) sweep of the Z pass of a Z-slab."""
-        n = len(in_ptrs)
         d = _desc(slab_shape_zyx, spacing)
-        ins = (C.c_void_p * n)(*in_ptrs)
-        cks = (C.c_void_p * n)(*ck_ptrs)
-        sg = (C.c_double * n)(*[float(s) for s in sigmas])
         self._chk(self._lib.ife_stage_z_sweep(
-            self._h, int(direction), n, ins, C.byref(d), int(line0), int(nlines), sg,
-            int(bool(has_neighbour)), C.c_void_p(state_in_ptr or 0), C.c_void_p(state_out_ptr), cks))
+            self._h, int(direction), len(in_ptrs), _ptr_array(in_ptrs), C.byref(d), int(line0), int(nlines),
+            _double_array(sigmas), int(bool(has_neighbour)), C.c_void_p(state_in_ptr or 0),
+            C.c_void_p(state_out_ptr), _ptr_array(ck_ptrs)))
 
     def stage_z_combine(self, in_ptrs, out_ptrs, slab_shape_zyx, spacing, line0, nlines, sigmas,
                         has_lo, has_hi, ck_ptrs):
-        n = len(in_ptrs)
         d = _desc(slab_shape_zyx, spacing)
-        ins = (C.c_void_p * n)(*in_ptrs)
-        outs = (C.c_void_p * n)(*out_ptrs)
-        cks = (C.c_void_p * n)(*ck_ptrs)
-        sg = (C.c_double * n)(*[float(s) for s in sigmas])
         self._chk(self._lib.ife_stage_z_combine(
-            self._h, n, ins, outs, C.byref(d), int(line0), int(nlines), sg, int(bool(has_lo)),
-            int(bool(has_hi)), cks))
+            self._h, len(in_ptrs), _ptr_array(in_ptrs), _ptr_array(out_ptrs), C.byref(d), int(line0),
+            int(nlines), _double_array(sigmas), int(bool(has_lo)), int(bool(has_hi)), _ptr_array(ck_ptrs)))
 
     def stage_z_fused(self, direction, in_ptrs, out_ptrs, slab_shape_zyx, spacing, line0, nlines,
                       sigmas, has_lo, has_hi, state_in_ptr, state_out_ptr, ck_ptrs):
         """Sweep of `direction` (0 causal, 1 anticausal) and combine in one launch."""
-        n = len(in_ptrs)
         d = _desc(slab_shape_zyx, spacing)
-        ins = (C.c_void_p * n)(*in_ptrs)
-        outs = (C.c_void_p * n)(*out_ptrs)
-        cks = (C.c_void_p * n)(*ck_ptrs)
-        sg = (C.c_double * n)(*[float(s) for s in sigmas])
         self._chk(self._lib.ife_stage_z_fused(
-            self._h, int(direction), n, ins, outs, C.byref(d), int(line0), int(nlines), sg,
-            int(bool(has_lo)), int(bool(has_hi)), C.c_void_p(state_in_ptr or 0),
-            C.c_void_p(state_out_ptr), cks))
+            self._h, int(direction), len(in_ptrs), _ptr_array(in_ptrs), _ptr_array(out_ptrs), C.byref(d),
+            int(line0), int(nlines), _double_array(sigmas), int(bool(has_lo)), int(bool(has_hi)),
+            C.c_void_p(state_in_ptr or 0), C.c_void_p(state_out_ptr), _ptr_array(ck_ptrs)))
 
     def stage_recursive_gaussian_quotient(self, num_ptrs, den_ptrs, out_ptrs, shape_zyx, spacing,
                                           axis_xyz, sigmas):
         """Last axis pass in its quotient form: out[j] = G(num[j]) / G(den[j]) (<= 4 jobs)."""
-        n = len(num_ptrs)
         d = _desc(shape_zyx, spacing)
-        nums = (C.c_void_p * n)(*num_ptrs)
-        dens = (C.c_void_p * n)(*den_ptrs)
-        outs = (C.c_void_p * n)(*out_ptrs)
-        sg = (C.c_double * n)(*[float(s) for s in sigmas])
         self._chk(self._lib.ife_stage_recursive_gaussian_quotient(
-            self._h, n, nums, dens, outs, C.byref(d), int(axis_xyz), sg))
+            self._h, len(num_ptrs), _ptr_array(num_ptrs), _ptr_array(den_ptrs), _ptr_array(out_ptrs),
+            C.byref(d), int(axis_xyz), _double_array(sigmas)))
 
     # ---- rows f1 / f2: sample columns, histogram edges, dense histograms --------------
     def sort_f32(self, values):
@@ -523,32 +516,30 @@ class Context:
     def roi_histograms(self, features, mask, rois, edges, spacing=(1.0, 1.0, 1.0), layout=INTERLEAVED):
         """Bag rows of one feature volume: counts (n_rois, ncomp, n_edges+1) uint32."""
         f = np.ascontiguousarray(features, np.float32)
-        mask = np.ascontiguousarray(mask)
+        mask, mdt, mptr = _mask_arg(mask)
         rois = np.ascontiguousarray(rois, np.int64).reshape(-1, 6)
         edges = np.ascontiguousarray(edges, np.float32)
         ncomp, ne = edges.shape
         d = _desc(mask.shape, spacing)
         counts = np.empty((rois.shape[0], ncomp, ne + 1), np.uint32)
         self._chk(self._lib.ife_roi_histograms(
-            self._h, f.ctypes.data, layout, ncomp, mask.ctypes.data, _MSK_DT[mask.dtype], C.byref(d),
+            self._h, f.ctypes.data, layout, ncomp, mptr, mdt, C.byref(d),
             rois.ctypes.data, rois.shape[0], edges.ctypes.data, ne, counts.ctypes.data, MEM_HOST))
         return counts
 
     def bag_image(self, image, mask, sigmas, rois, edges, spacing=(1.0, 1.0, 1.0)):
         """One image of MakeBag: counts (n_rois, n_sigmas*8, n_edges+1) uint32."""
-        image = np.ascontiguousarray(image)
-        if image.dtype not in _IMG_DT:
-            image = image.astype(np.float32)
-        mask = np.ascontiguousarray(mask)
+        image, idt = _image_arg(image)
+        mask, mdt, mptr = _mask_arg(mask)
         rois = np.ascontiguousarray(rois, np.int64).reshape(-1, 6)
         edges = np.ascontiguousarray(edges, np.float32)
         ne = edges.shape[1]
         d = _desc(image.shape, spacing)
-        sig = (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
+        sig = _sigma_arg(sigmas)
         counts = np.empty((rois.shape[0], 8 * len(sigmas), ne + 1), np.uint32)
         self._chk(self._lib.ife_bag_image(
-            self._h, image.ctypes.data, _IMG_DT[image.dtype], mask.ctypes.data, _MSK_DT[mask.dtype],
-            C.byref(d), sig, len(sigmas), rois.ctypes.data, rois.shape[0], edges.ctypes.data, ne,
+            self._h, image.ctypes.data, idt, mptr, mdt, C.byref(d), sig, len(sigmas), rois.ctypes.data,
+            rois.shape[0], edges.ctypes.data, ne,
             counts.ctypes.data, MEM_HOST))
         return counts
 
@@ -587,19 +578,14 @@ class Multi:
         self._chk(self._lib.ife_multi_set_option(self._h, int(option), int(value)))
 
     def emphysema_features(self, image, mask, sigmas, spacing=(1.0, 1.0, 1.0), layout=INTERLEAVED):
-        image = np.ascontiguousarray(image)
-        if image.dtype not in _IMG_DT:
-            image = image.astype(np.float32)
-        mdt, mptr = U8, None
-        if mask is not None:
-            mask = np.ascontiguousarray(mask)
-            mdt, mptr = _MSK_DT[mask.dtype], mask.ctypes.data
+        image, idt = _image_arg(image)
+        mask, mdt, mptr = _mask_arg(mask)
         d = _desc(image.shape, spacing)
-        sig = (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
+        sig = _sigma_arg(sigmas)
         shp = image.shape + (8,) if layout == INTERLEAVED else (8,) + image.shape
         out = np.empty((len(sigmas),) + shp, np.float32)
         self._chk(self._lib.ife_multi_emphysema_features(
-            self._h, image.ctypes.data, _IMG_DT[image.dtype], mptr, mdt, C.byref(d), sig,
+            self._h, image.ctypes.data, idt, mptr, mdt, C.byref(d), sig,
             len(sigmas), out.ctypes.data, layout))
         return out
 
@@ -608,18 +594,13 @@ class Multi:
         """Generator over the scales: one upload and prepass, every scale enqueued on every
         device, then one blocking fetch per scale (ife_multi_emphysema_features_begin / _fetch /
         _end) -- the scale loop of tools/ExtractFeatures.cxx:132-154 over several devices."""
-        image = np.ascontiguousarray(image)
-        if image.dtype not in _IMG_DT:
-            image = image.astype(np.float32)
-        mdt, mptr = U8, None
-        if mask is not None:
-            mask = np.ascontiguousarray(mask)
-            mdt, mptr = _MSK_DT[mask.dtype], mask.ctypes.data
+        image, idt = _image_arg(image)
+        mask, mdt, mptr = _mask_arg(mask)
         d = _desc(image.shape, spacing)
-        sig = (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
+        sig = _sigma_arg(sigmas)
         shp = image.shape + (8,) if layout == INTERLEAVED else (8,) + image.shape
         self._chk(self._lib.ife_multi_emphysema_features_begin(
-            self._h, image.ctypes.data, _IMG_DT[image.dtype], mptr, mdt, C.byref(d), sig, len(sigmas), layout))
+            self._h, image.ctypes.data, idt, mptr, mdt, C.byref(d), sig, len(sigmas), layout))
         try:
             for k in range(len(sigmas)):
                 out = np.empty(shp, np.float32)
@@ -676,8 +657,7 @@ class Samples:
             indices = np.ascontiguousarray(indices, np.int64).ravel()
             iptr, ni = indices.ctypes.data, indices.size
         else:
-            mask = np.ascontiguousarray(mask)
-            mptr, mdt = mask.ctypes.data, _MSK_DT[mask.dtype]
+            mask, mdt, mptr = _mask_arg(mask)
         self._ctx._chk(self._lib.ife_samples_add_features(
             self._ctx._h, self._h, int(first_column), f.ctypes.data, layout, ncomp, mptr, mdt, nvox,
             fgp, fg.size, iptr, ni, MEM_HOST))
@@ -685,25 +665,23 @@ class Samples:
     def add_image(self, image, mask, sigmas, foreground=(1,), indices=None,
                   spacing=(1.0, 1.0, 1.0)):
         """One image of the tool's loop: features at every scale stay on the device."""
-        image = np.ascontiguousarray(image)
-        if image.dtype not in _IMG_DT:
-            image = image.astype(np.float32)
-        mask = np.ascontiguousarray(mask)
+        image, idt = _image_arg(image)
+        mask, mdt, mptr = _mask_arg(mask)
         d = _desc(image.shape, spacing)
-        sig = (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
+        sig = _sigma_arg(sigmas)
         fg, fgp = self._fg(foreground)
         iptr, ni = None, 0
         if indices is not None:
             indices = np.ascontiguousarray(indices, np.int64).reshape(len(sigmas), -1)
             iptr, ni = indices.ctypes.data, indices.shape[1]
         self._ctx._chk(self._lib.ife_samples_add_image(
-            self._ctx._h, self._h, image.ctypes.data, _IMG_DT[image.dtype], mask.ctypes.data,
-            _MSK_DT[mask.dtype], C.byref(d), sig, len(sigmas), fgp, fg.size, iptr, ni, MEM_HOST))
+            self._ctx._h, self._h, image.ctypes.data, idt, mptr, mdt, C.byref(d), sig, len(sigmas),
+            fgp, fg.size, iptr, ni, MEM_HOST))
 
     def add_image_device(self, image_ptr, image_dtype, mask_ptr, mask_dtype, shape_zyx, sigmas,
                          foreground=(1,), spacing=(1.0, 1.0, 1.0)):
         d = _desc(shape_zyx, spacing)
-        sig = (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
+        sig = _sigma_arg(sigmas)
         fg, fgp = self._fg(foreground)
         self._ctx._chk(self._lib.ife_samples_add_image(
             self._ctx._h, self._h, C.c_void_p(image_ptr), image_dtype, C.c_void_p(mask_ptr),

@@ -37,6 +37,36 @@ using namespace ife;
 
 namespace {
 
+// The line kernels of one build of iir_kernels.inc (exact or fused multiply-add), as a type:
+// the launchers take it as a template parameter.
+#define IFE_IIR_KERNELS(NS)                                                                      \
+  struct NS##_kernels {                                                                          \
+    template <int K> static constexpr auto contig = NS::iir_contig_kernel<K>;                    \
+    template <int K> static constexpr auto strided1 = NS::iir_strided1_kernel<K>;                \
+    template <int K, bool PAIRED> static constexpr auto strided = NS::iir_strided_kernel<K, PAIRED>; \
+    template <int K> static constexpr auto zslab_causal = NS::zslab_causal_kernel<K>;            \
+    template <int K> static constexpr auto zslab_anti = NS::zslab_anti_kernel<K>;                \
+    template <int K, int DIR> static constexpr auto zslab_fused = NS::zslab_fused_kernel<K, DIR>; \
+    template <int K> static constexpr auto zslab_combine = NS::zslab_combine_kernel<K>;          \
+  }
+IFE_IIR_KERNELS(iir_exact);
+IFE_IIR_KERNELS(iir_fma);
+#undef IFE_IIR_KERNELS
+template <typename F>
+void with_iir_kernels(int fma, F &&f) {
+  if (fma) f(iir_fma_kernels{});
+  else f(iir_exact_kernels{});
+}
+
+// Run-time value to template argument: f(std::integral_constant<int, V>) for the V of the list
+// that equals v, for the last of the list when none does.
+template <int V0, int... Vs, typename F>
+void with_const(int v, F &&f) {
+  if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+  else if (v == V0) f(std::integral_constant<int, V0>{});
+  else with_const<Vs...>(v, f);
+}
+
 enum KernelKind {
   KK_IIR_Z = 0,
   KK_IIR_X,
@@ -214,15 +244,12 @@ int drain_profile(ife_ctx *ctx) {
 // (oracle/ife_oracle.c: pole_sincos; found by tests/test_gpu_fuzz.py).
 void pole_sincos(double x, double &s, double &c) { ::sincos(x, &s, &c); }
 
-int gauss_coeffs(double sigma, double spacing, IirCoef *c) {
-  const double A1 = 1.3530, B1 = 1.8151, W1 = 0.6681, L1 = -1.3932;
-  const double A2 = -0.3531, B2 = 0.0902, W2 = 2.0787, L2 = -1.3732;
-  if (spacing < 0.0) spacing = -spacing;
-  if (spacing < 1e-8) return -1;
-  const double sd = sigma / spacing;
+// D from the poles (the same for every order).
+void d_coefficients(double sd, double W1, double L1, double W2, double L2, IirCoef *c) {
   double Sin1, Sin2, Cos1, Cos2;
   pole_sincos(W1 / sd, Sin1, Cos1);
   pole_sincos(W2 / sd, Sin2, Cos2);
+  (void)Sin1; (void)Sin2;
   const double Exp1 = std::exp(L1 / sd), Exp2 = std::exp(L2 / sd);
   c->D4 = Exp1 * Exp1 * Exp2 * Exp2;
   c->D3 = -2 * Cos1 * Exp1 * Exp2 * Exp2;
@@ -230,38 +257,8 @@ int gauss_coeffs(double sigma, double spacing, IirCoef *c) {
   c->D2 = 4 * Cos2 * Cos1 * Exp1 * Exp2;
   c->D2 += Exp1 * Exp1 + Exp2 * Exp2;
   c->D1 = -2 * (Exp2 * Cos2 + Exp1 * Cos1);
-  const double SD = 1.0 + c->D1 + c->D2 + c->D3 + c->D4;
-  c->N0 = A1 + A2;
-  c->N1 = Exp2 * (B2 * Sin2 - (A2 + 2 * A1) * Cos2);
-  c->N1 += Exp1 * (B1 * Sin1 - (A1 + 2 * A2) * Cos1);
-  c->N2 = (A1 + A2) * Cos2 * Cos1;
-  c->N2 -= B1 * Cos2 * Sin1 + B2 * Cos1 * Sin2;
-  c->N2 *= 2 * Exp1 * Exp2;
-  c->N2 += A2 * Exp1 * Exp1 + A1 * Exp2 * Exp2;
-  c->N3 = Exp2 * Exp1 * Exp1 * (B2 * Sin2 - A2 * Cos2);
-  c->N3 += Exp1 * Exp2 * Exp2 * (B1 * Sin1 - A1 * Cos1);
-  const double SN = c->N0 + c->N1 + c->N2 + c->N3;
-  const double alpha0 = 2 * SN / SD - c->N0;
-  const double nrm = 1.0 / alpha0;
-  c->N0 *= nrm; c->N1 *= nrm; c->N2 *= nrm; c->N3 *= nrm;
-  c->M1 = c->N1 - c->D1 * c->N0;
-  c->M2 = c->N2 - c->D2 * c->N0;
-  c->M3 = c->N3 - c->D3 * c->N0;
-  c->M4 = -c->D4 * c->N0;
-  const double SN2 = c->N0 + c->N1 + c->N2 + c->N3;
-  const double SM2 = c->M1 + c->M2 + c->M3 + c->M4;
-  const double SD2 = 1.0 + c->D1 + c->D2 + c->D3 + c->D4;
-  c->BN1 = c->D1 * SN2 / SD2; c->BN2 = c->D2 * SN2 / SD2;
-  c->BN3 = c->D3 * SN2 / SD2; c->BN4 = c->D4 * SN2 / SD2;
-  c->BM1 = c->D1 * SM2 / SD2; c->BM2 = c->D2 * SM2 / SD2;
-  c->BM3 = c->D3 * SM2 / SD2; c->BM4 = c->D4 * SM2 / SD2;
-  return 0;
 }
-
-// Orders 1 and 2 of the same routine (row f4; the reference only sketches their use,
-// NormalizedGaussianConvolutionImageFilter.h:28-44): per-order constants of the exponential
-// series, normalisation to a unit response on a unit ramp / unit parabola in pixel units,
-// and the antisymmetric form of the anticausal coefficients for the first order.
+// N of one term of the exponential series, with its sums SN, DN = sum(i N_i), EN = sum(i^2 N_i).
 void n_coefficients(double sd, double A1, double B1, double W1, double L1, double A2, double B2,
                     double W2, double L2, double &N0, double &N1, double &N2, double &N3, double &SN,
                     double &DN, double &EN) {
@@ -282,53 +279,8 @@ void n_coefficients(double sd, double A1, double B1, double W1, double L1, doubl
   DN = N1 + 2 * N2 + 3 * N3;
   EN = N1 + 4 * N2 + 9 * N3;
 }
-int gauss_coeffs_order(double sigma, double spacing, int order, IirCoef *c) {
-  if (order == 0) return gauss_coeffs(sigma, spacing, c);
-  const double A1[3] = {1.3530, -0.6724, -1.3563}, B1[3] = {1.8151, -3.4327, 5.2318};
-  const double A2[3] = {-0.3531, 0.6724, 0.3446}, B2[3] = {0.0902, 0.6100, -2.2355};
-  const double W1 = 0.6681, L1 = -1.3932, W2 = 2.0787, L2 = -1.3732;
-  if (order != 1 && order != 2) return -1;
-  double direction = 1.0;
-  if (spacing < 0.0) { direction = -1.0; spacing = -spacing; }
-  if (spacing < 1e-8) return -1;
-  const double sd = sigma / spacing;
-  {
-    double Sin1, Sin2, Cos1, Cos2;
-    pole_sincos(W1 / sd, Sin1, Cos1);
-    pole_sincos(W2 / sd, Sin2, Cos2);
-    (void)Sin1; (void)Sin2;
-    const double Exp1 = std::exp(L1 / sd), Exp2 = std::exp(L2 / sd);
-    c->D4 = Exp1 * Exp1 * Exp2 * Exp2;
-    c->D3 = -2 * Cos1 * Exp1 * Exp2 * Exp2;
-    c->D3 += -2 * Cos2 * Exp2 * Exp1 * Exp1;
-    c->D2 = 4 * Cos2 * Cos1 * Exp1 * Exp2;
-    c->D2 += Exp1 * Exp1 + Exp2 * Exp2;
-    c->D1 = -2 * (Exp2 * Cos2 + Exp1 * Cos1);
-  }
-  const double SD = 1.0 + c->D1 + c->D2 + c->D3 + c->D4;
-  const double DD = c->D1 + 2 * c->D2 + 3 * c->D3 + 4 * c->D4;
-  const double ED = c->D1 + 4 * c->D2 + 9 * c->D3 + 16 * c->D4;
-  bool symmetric;
-  if (order == 1) {
-    double SN, DN, EN;
-    n_coefficients(sd, A1[1], B1[1], W1, L1, A2[1], B2[1], W2, L2, c->N0, c->N1, c->N2, c->N3, SN, DN, EN);
-    double alpha1 = 2 * (SN * DD - DN * SD) / (SD * SD);
-    alpha1 *= direction;
-    c->N0 *= 1.0 / alpha1; c->N1 *= 1.0 / alpha1; c->N2 *= 1.0 / alpha1; c->N3 *= 1.0 / alpha1;
-    symmetric = false;
-  } else {
-    double N0_0, N1_0, N2_0, N3_0, N0_2, N1_2, N2_2, N3_2, SN0, DN0, EN0, SN2, DN2, EN2;
-    n_coefficients(sd, A1[0], B1[0], W1, L1, A2[0], B2[0], W2, L2, N0_0, N1_0, N2_0, N3_0, SN0, DN0, EN0);
-    n_coefficients(sd, A1[2], B1[2], W1, L1, A2[2], B2[2], W2, L2, N0_2, N1_2, N2_2, N3_2, SN2, DN2, EN2);
-    const double beta = -(2 * SN2 - SD * N0_2) / (2 * SN0 - SD * N0_0);
-    const double N0 = N0_2 + beta * N0_0, N1 = N1_2 + beta * N1_0;
-    const double N2 = N2_2 + beta * N2_0, N3 = N3_2 + beta * N3_0;
-    const double SN = SN2 + beta * SN0, DN = DN2 + beta * DN0, EN = EN2 + beta * EN0;
-    const double alpha2 = (EN * SD * SD - ED * SN * SD - 2 * DN * DD * SD + 2 * DD * DD * SN) / (SD * SD * SD);
-    c->N0 = N0 * (1.0 / alpha2); c->N1 = N1 * (1.0 / alpha2);
-    c->N2 = N2 * (1.0 / alpha2); c->N3 = N3 * (1.0 / alpha2);
-    symmetric = true;
-  }
+// M (anticausal) and the boundary coefficients from N and D; the first order is antisymmetric.
+void m_and_boundary(IirCoef *c, bool symmetric) {
   if (symmetric) {
     c->M1 = c->N1 - c->D1 * c->N0; c->M2 = c->N2 - c->D2 * c->N0;
     c->M3 = c->N3 - c->D3 * c->N0; c->M4 = -c->D4 * c->N0;
@@ -343,6 +295,49 @@ int gauss_coeffs_order(double sigma, double spacing, int order, IirCoef *c) {
   c->BN3 = c->D3 * SN2 / SD2; c->BN4 = c->D4 * SN2 / SD2;
   c->BM1 = c->D1 * SM2 / SD2; c->BM2 = c->D2 * SM2 / SD2;
   c->BM3 = c->D3 * SM2 / SD2; c->BM4 = c->D4 * SM2 / SD2;
+}
+// Order 0 is ITK's ZeroOrder case.  Orders 1 and 2 of the same routine (row f4; the reference
+// only sketches their use, NormalizedGaussianConvolutionImageFilter.h:28-44): per-order constants
+// of the exponential series, normalisation to a unit response on a unit ramp / unit parabola in
+// pixel units, and the antisymmetric form of the anticausal coefficients for the first order.
+int gauss_coeffs_order(double sigma, double spacing, int order, IirCoef *c) {
+  const double A1[3] = {1.3530, -0.6724, -1.3563}, B1[3] = {1.8151, -3.4327, 5.2318};
+  const double A2[3] = {-0.3531, 0.6724, 0.3446}, B2[3] = {0.0902, 0.6100, -2.2355};
+  const double W1 = 0.6681, L1 = -1.3932, W2 = 2.0787, L2 = -1.3732;
+  if (order < 0 || order > 2) return -1;
+  double direction = 1.0;
+  if (spacing < 0.0) { direction = -1.0; spacing = -spacing; }
+  if (spacing < 1e-8) return -1;
+  const double sd = sigma / spacing;
+  d_coefficients(sd, W1, L1, W2, L2, c);
+  const double SD = 1.0 + c->D1 + c->D2 + c->D3 + c->D4;
+  const double DD = c->D1 + 2 * c->D2 + 3 * c->D3 + 4 * c->D4;
+  const double ED = c->D1 + 4 * c->D2 + 9 * c->D3 + 16 * c->D4;
+  if (order == 0) {
+    double SN, DN, EN;
+    n_coefficients(sd, A1[0], B1[0], W1, L1, A2[0], B2[0], W2, L2, c->N0, c->N1, c->N2, c->N3, SN, DN, EN);
+    const double alpha0 = 2 * SN / SD - c->N0;
+    const double nrm = 1.0 / alpha0;
+    c->N0 *= nrm; c->N1 *= nrm; c->N2 *= nrm; c->N3 *= nrm;
+  } else if (order == 1) {
+    double SN, DN, EN;
+    n_coefficients(sd, A1[1], B1[1], W1, L1, A2[1], B2[1], W2, L2, c->N0, c->N1, c->N2, c->N3, SN, DN, EN);
+    double alpha1 = 2 * (SN * DD - DN * SD) / (SD * SD);
+    alpha1 *= direction;
+    c->N0 *= 1.0 / alpha1; c->N1 *= 1.0 / alpha1; c->N2 *= 1.0 / alpha1; c->N3 *= 1.0 / alpha1;
+  } else {
+    double N0_0, N1_0, N2_0, N3_0, N0_2, N1_2, N2_2, N3_2, SN0, DN0, EN0, SN2, DN2, EN2;
+    n_coefficients(sd, A1[0], B1[0], W1, L1, A2[0], B2[0], W2, L2, N0_0, N1_0, N2_0, N3_0, SN0, DN0, EN0);
+    n_coefficients(sd, A1[2], B1[2], W1, L1, A2[2], B2[2], W2, L2, N0_2, N1_2, N2_2, N3_2, SN2, DN2, EN2);
+    const double beta = -(2 * SN2 - SD * N0_2) / (2 * SN0 - SD * N0_0);
+    const double N0 = N0_2 + beta * N0_0, N1 = N1_2 + beta * N1_0;
+    const double N2 = N2_2 + beta * N2_0, N3 = N3_2 + beta * N3_0;
+    const double SN = SN2 + beta * SN0, DN = DN2 + beta * DN0, EN = EN2 + beta * EN0;
+    const double alpha2 = (EN * SD * SD - ED * SN * SD - 2 * DN * DD * SD + 2 * DD * DD * SN) / (SD * SD * SD);
+    c->N0 = N0 * (1.0 / alpha2); c->N1 = N1 * (1.0 / alpha2);
+    c->N2 = N2 * (1.0 / alpha2); c->N3 = N3 * (1.0 / alpha2);
+  }
+  m_and_boundary(c, order != 1);
   return 0;
 }
 
@@ -534,47 +529,18 @@ int launch_iir(ife_ctx *ctx, const ife_volume_desc *v, int axis, int njobs,
   // are exact (iir_kernels.inc "Memory operations and waits") three waves hide the latency and
   // the fewer checkpoints win: z 1.85 -> 1.74 ms, y 1.87 with 12 against 2.06 with 16.
   const int sblock = ctx->iir_block ? ctx->iir_block : 12;
-#define IFE_LAUNCH_IIR(NS)                                                                      \
-  do {                                                                                          \
-    if (axis == 0) {                                                                            \
-      if (ctx->iir_block == 8)                                                                  \
-        hipLaunchKernelGGL((NS::iir_contig_kernel<8>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-      else                                                                                      \
-        hipLaunchKernelGGL((NS::iir_contig_kernel<16>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-    } else if (ctx->iir_ckpt == 1) {                                                            \
-      if (ctx->iir_block == 8)                                                                  \
-        hipLaunchKernelGGL((NS::iir_strided1_kernel<8>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-      else                                                                                      \
-        hipLaunchKernelGGL((NS::iir_strided1_kernel<16>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-    } else {                                                                                    \
-      if (sblock == 8)                                                                          \
-        hipLaunchKernelGGL((NS::iir_strided_kernel<8>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-      else if (sblock == 10)                                                                    \
-        hipLaunchKernelGGL((NS::iir_strided_kernel<10>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-      else if (sblock == 12)                                                                    \
-        hipLaunchKernelGGL((NS::iir_strided_kernel<12>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-      else                                                                                      \
-        hipLaunchKernelGGL((NS::iir_strided_kernel<16>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-    }                                                                                           \
-  } while (0)
-  if (in2) {
-#define IFE_LAUNCH_PAIRED(NS)                                                                          \
-  do {                                                                                                 \
-    if (sblock == 8)                                                                                   \
-      hipLaunchKernelGGL((NS::iir_strided_kernel<8, true>), grid, dim3(256), 0, ctx->stream, jobs, g);  \
-    else if (sblock == 10)                                                                             \
-      hipLaunchKernelGGL((NS::iir_strided_kernel<10, true>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-    else if (sblock == 12)                                                                             \
-      hipLaunchKernelGGL((NS::iir_strided_kernel<12, true>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-    else                                                                                               \
-      hipLaunchKernelGGL((NS::iir_strided_kernel<16, true>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-  } while (0)
-    if (ctx->iir_fma) IFE_LAUNCH_PAIRED(iir_fma);
-    else IFE_LAUNCH_PAIRED(iir_exact);
-#undef IFE_LAUNCH_PAIRED
-  } else if (ctx->iir_fma) IFE_LAUNCH_IIR(iir_fma);
-  else IFE_LAUNCH_IIR(iir_exact);
-#undef IFE_LAUNCH_IIR
+  with_iir_kernels(ctx->iir_fma, [&](auto ks) {
+    using KS = decltype(ks);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, jobs, g); };
+    if (in2)
+      with_const<8, 10, 12, 16>(sblock, [&](auto K) { launch(KS::template strided<decltype(K)::value, true>); });
+    else if (axis == 0)
+      with_const<8, 16>(ctx->iir_block, [&](auto K) { launch(KS::template contig<decltype(K)::value>); });
+    else if (ctx->iir_ckpt == 1)
+      with_const<8, 16>(ctx->iir_block, [&](auto K) { launch(KS::template strided1<decltype(K)::value>); });
+    else
+      with_const<8, 10, 12, 16>(sblock, [&](auto K) { launch(KS::template strided<decltype(K)::value, false>); });
+  });
   IFE_HIP(ctx, hipGetLastError());
   return IFE_OK;
 }
@@ -625,7 +591,7 @@ int launch_zslab(ife_ctx *ctx, int phase, int njobs, const float *const *in, flo
     const size_t rec = (size_t)nlines * IFE_Z_STATE_BYTES;  // [4][nlines] doubles per job
     if (state_in) J.sin_y = (const double *)((const char *)state_in + (size_t)j * rec);
     if (state_out) J.sout_y = (double *)((char *)state_out + (size_t)j * rec);
-    if (!(sigmas[j] > 0.0) || gauss_coeffs(sigmas[j], v->sz, &J.c))
+    if (!(sigmas[j] > 0.0) || gauss_coeffs_order(sigmas[j], v->sz, 0, &J.c))
       return fail(ctx, IFE_E_ARG, "bad sigma or spacing");
   }
   ZSlabGeom g;
@@ -635,22 +601,15 @@ int launch_zslab(ife_ctx *ctx, int phase, int njobs, const float *const *in, flo
   g.ngroups = (int32_t)((nlines + 255) / 256);
   const dim3 grid((unsigned)((g.ngroups + 7) / 8 * 8 * njobs), 1, 1);
   ProfScope ps(ctx, phase >= 2 ? KK_ZSLAB_COMBINE : KK_ZSLAB_SWEEP);
-#define IFE_LAUNCH_ZSLAB(NS)                                                                        \
-  do {                                                                                              \
-    if (phase == 0)                                                                                 \
-      hipLaunchKernelGGL((NS::zslab_causal_kernel<ZSLAB_K>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-    else if (phase == 1)                                                                            \
-      hipLaunchKernelGGL((NS::zslab_anti_kernel<ZSLAB_K>), grid, dim3(256), 0, ctx->stream, jobs, g);   \
-    else if (phase == 3)                                                                            \
-      hipLaunchKernelGGL((NS::zslab_fused_kernel<ZSLAB_K, 0>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-    else if (phase == 4)                                                                            \
-      hipLaunchKernelGGL((NS::zslab_fused_kernel<ZSLAB_K, 1>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-    else                                                                                            \
-      hipLaunchKernelGGL((NS::zslab_combine_kernel<ZSLAB_K>), grid, dim3(256), 0, ctx->stream, jobs, g); \
-  } while (0)
-  if (ctx->iir_fma) IFE_LAUNCH_ZSLAB(iir_fma);
-  else IFE_LAUNCH_ZSLAB(iir_exact);
-#undef IFE_LAUNCH_ZSLAB
+  with_iir_kernels(ctx->iir_fma, [&](auto ks) {
+    using KS = decltype(ks);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, jobs, g); };
+    if (phase == 0) launch(KS::template zslab_causal<ZSLAB_K>);
+    else if (phase == 1) launch(KS::template zslab_anti<ZSLAB_K>);
+    else if (phase == 3) launch(KS::template zslab_fused<ZSLAB_K, 0>);
+    else if (phase == 4) launch(KS::template zslab_fused<ZSLAB_K, 1>);
+    else launch(KS::template zslab_combine<ZSLAB_K>);
+  });
   IFE_HIP(ctx, hipGetLastError());
   return IFE_OK;
 }
@@ -786,40 +745,29 @@ int launch_features(ife_ctx *ctx, VAL val, const TM *mask, float *out,
            (mask == nullptr ||
             (row_bytes % 4 == 0 && plane_bytes % 4 == 0 && reinterpret_cast<uintptr_t>(mask) % 4 == 0));
   }
-#define IFE_LAUNCH_FEAT2(UNIT_, TRIG_, PL_)                                                    \
-  do {                                                                                         \
-    if constexpr (ring_types) {                                                                \
-      if (ring) {                                                                              \
-        hipLaunchKernelGGL((features_ring_kernel<MODE, UNIT_, TRIG_, PL_, TM>), grid,          \
-                           dim3(FT_THREADS), 0, ctx->stream, ring_src, mask, out, g, dc);      \
-        break;                                                                                 \
-      }                                                                                        \
-    }                                                                                          \
-    hipLaunchKernelGGL((features_kernel<MODE, UNIT_, TRIG_, PL_, VAL, TM>), grid,              \
-                       dim3(FT_THREADS), 0, ctx->stream, val, mask, out, g, dc);               \
-  } while (0)
-#define IFE_LAUNCH_FEAT(UNIT_, TRIG_)                                                  \
-  do {                                                                                 \
-    if constexpr (MODE == FEAT_SAMPLES8) IFE_LAUNCH_FEAT2(UNIT_, TRIG_, true);         \
-    else if (planar) IFE_LAUNCH_FEAT2(UNIT_, TRIG_, true);                             \
-    else IFE_LAUNCH_FEAT2(UNIT_, TRIG_, false);                                        \
-  } while (0)
-  if (has_eig && ctx->trig_mode == 1) {
-    if constexpr (has_eig) {
-      if (unit) IFE_LAUNCH_FEAT(true, 1);
-      else IFE_LAUNCH_FEAT(false, 1);
+  auto launch = [&](auto UNIT, auto TRIG, auto PL) {
+    constexpr bool U = decltype(UNIT)::value != 0, P = decltype(PL)::value != 0;
+    constexpr int T = decltype(TRIG)::value;
+    if constexpr (ring_types) {
+      if (ring) {
+        hipLaunchKernelGGL((features_ring_kernel<MODE, U, T, P, TM>), grid, dim3(FT_THREADS), 0, ctx->stream,
+                           ring_src, mask, out, g, dc);
+        return;
+      }
     }
-  } else if (has_eig && ctx->trig_mode == 2) {
-    if constexpr (has_eig) {
-      if (unit) IFE_LAUNCH_FEAT(true, 2);
-      else IFE_LAUNCH_FEAT(false, 2);
-    }
-  } else {
-    if (unit) IFE_LAUNCH_FEAT(true, 0);
-    else IFE_LAUNCH_FEAT(false, 0);
-  }
-#undef IFE_LAUNCH_FEAT2
-#undef IFE_LAUNCH_FEAT
+    hipLaunchKernelGGL((features_kernel<MODE, U, T, P, VAL, TM>), grid, dim3(FT_THREADS), 0, ctx->stream, val,
+                       mask, out, g, dc);
+  };
+  // unit spacing, then the trigonometry (only kernels with eigenvalues have one to choose), then
+  // the layout (the sample columns are planar by construction)
+  with_const<1, 0>(unit, [&](auto UNIT) {
+    auto with_trig = [&](auto TRIG) {
+      if constexpr (MODE == FEAT_SAMPLES8) launch(UNIT, TRIG, std::true_type{});
+      else with_const<1, 0>(planar, [&](auto PL) { launch(UNIT, TRIG, PL); });
+    };
+    if constexpr (has_eig) with_const<1, 2, 0>(ctx->trig_mode, with_trig);
+    else with_trig(std::integral_constant<int, 0>{});
+  });
   IFE_HIP(ctx, hipGetLastError());
   return IFE_OK;
 }
@@ -834,11 +782,58 @@ size_t dtype_size(int dt) {
   return 0;
 }
 
+// ---- argument checks shared by the entry points (status returned, message through fail) ----
+int check_mem(ife_ctx *ctx, int mem) {
+  if (mem != IFE_MEM_HOST && mem != IFE_MEM_DEVICE) return fail(ctx, IFE_E_ARG, "bad mem %d", mem);
+  return IFE_OK;
+}
 int check_layout_mem(ife_ctx *ctx, int layout, int mem) {
   if (layout != IFE_INTERLEAVED && layout != IFE_PLANAR)
     return fail(ctx, IFE_E_ARG, "bad layout %d", layout);
-  if (mem != IFE_MEM_HOST && mem != IFE_MEM_DEVICE) return fail(ctx, IFE_E_ARG, "bad mem %d", mem);
+  return check_mem(ctx, mem);
+}
+int check_image_dtype(ife_ctx *ctx, int dt) {
+  if (dt != IFE_F32 && dt != IFE_I16) return fail(ctx, IFE_E_ARG, "image dtype must be IFE_F32 or IFE_I16");
   return IFE_OK;
+}
+// a null mask (certainty one everywhere) passes with any dtype where may_be_null
+int check_mask_dtype(ife_ctx *ctx, const void *mask, int dt, bool may_be_null) {
+  if (!mask) return may_be_null ? IFE_OK : fail(ctx, IFE_E_ARG, "null pointer");
+  if (dt != IFE_U8 && dt != IFE_U16) return fail(ctx, IFE_E_ARG, "mask dtype must be IFE_U8 or IFE_U16");
+  return IFE_OK;
+}
+int check_sigma(ife_ctx *ctx, double sigma) {
+  if (!(sigma > 0.0)) return fail(ctx, IFE_E_ARG, "sigma must be positive");
+  return IFE_OK;
+}
+int check_sigmas(ife_ctx *ctx, const float *sigmas, int n_sigmas) {
+  if (n_sigmas < 1) return fail(ctx, IFE_E_ARG, "at least one sigma is required");
+  for (int s = 0; s < n_sigmas; ++s)
+    if (!(sigmas[s] > 0.0f)) return fail(ctx, IFE_E_ARG, "sigma[%d] must be positive", s);
+  return IFE_OK;
+}
+int check_axis(ife_ctx *ctx, int axis) {
+  if (axis < 0 || axis > 2) return fail(ctx, IFE_E_ARG, "axis must be 0 (x), 1 (y) or 2 (z)");
+  return IFE_OK;
+}
+int check_axis_len(ife_ctx *ctx, const ife_volume_desc *v, int axis) {
+  if ((axis == 0 ? v->nx : axis == 1 ? v->ny : v->nz) < 4)
+    return fail(ctx, IFE_E_SIZE, "the recursive Gaussian needs at least 4 voxels along axis %d", axis);
+  return IFE_OK;
+}
+
+// Run-time dtypes to typed pointers: f(const uint8_t * | const uint16_t *) and
+// f(const float * | const int16_t *, mask as before).  A null mask stays const uint8_t *.
+template <typename F>
+int with_mask_type(bool has_mask, int mask_dtype, const void *msk, F &&f) {
+  if (has_mask && mask_dtype == IFE_U16) return f((const uint16_t *)msk);
+  return f((const uint8_t *)msk);
+}
+template <typename F>
+int with_types(int image_dtype, const void *img, bool has_mask, int mask_dtype, const void *msk, F &&f) {
+  return with_mask_type(has_mask, mask_dtype, msk, [&](auto m) {
+    return image_dtype == IFE_F32 ? f((const float *)img, m) : f((const int16_t *)img, m);
+  });
 }
 
 // Stage a host input on the device (HOST mode) or pass the device pointer through.
@@ -929,6 +924,49 @@ static int emphysema_typed(ife_ctx *ctx, const TI *img, const TM *msk, const ife
     if (rc) return rc;
   }
   return IFE_OK;
+}
+
+// The arguments of ife_emphysema_features and of its streaming form (which has no output yet).
+static int emphysema_check(ife_ctx *ctx, const void *image, int image_dtype, const void *mask, int mask_dtype,
+                           const ife_volume_desc *vol, const float *sigmas, int n_sigmas, bool have_out,
+                           int layout, int mem) {
+  int rc;
+  if ((rc = check_vol(ctx, vol, true))) return rc;
+  if ((rc = check_layout_mem(ctx, layout, mem))) return rc;
+  if (!image || !have_out || !sigmas) return fail(ctx, IFE_E_ARG, "null pointer");
+  if ((rc = check_sigmas(ctx, sigmas, n_sigmas))) return rc;
+  if ((rc = check_image_dtype(ctx, image_dtype))) return rc;
+  return check_mask_dtype(ctx, mask, mask_dtype, true);
+}
+
+// Stage image and mask (HOST mode), then every scale into dout (device).  With `uploaded`, an
+// event is recorded behind the uploads and handed to the caller, who waits for it: from
+// page-locked memory the uploads run asynchronously to the host.  *uploaded stays null when this
+// stopped before the scales.
+static int emphysema_staged(ife_ctx *ctx, int mem, const void *image, int image_dtype, const void *mask,
+                            int mask_dtype, const ife_volume_desc *vol, const float *sigmas, int n_sigmas,
+                            float *dout, int layout, hipEvent_t *uploaded = nullptr) {
+  const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
+  const void *dI, *dM;
+  int rc;
+  if ((rc = stage_in(ctx, mem, image, n * dtype_size(image_dtype), ctx->st_img, &dI))) return rc;
+  if ((rc = stage_in(ctx, mem, mask, n * (mask ? dtype_size(mask_dtype) : 0), ctx->st_mask, &dM))) {
+    if (uploaded) (void)hipStreamSynchronize(ctx->stream);  // the image upload may still read the caller's memory
+    return rc;
+  }
+  if (uploaded) {
+    hipEvent_t e = nullptr;
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess ||
+        hipEventRecord(e, ctx->stream) != hipSuccess) {
+      if (e) (void)hipEventDestroy(e);
+      (void)hipStreamSynchronize(ctx->stream);
+      return fail(ctx, IFE_E_HIP, "upload event: %s", hipGetErrorString(hipGetLastError()));
+    }
+    *uploaded = e;
+  }
+  return with_types(image_dtype, dI, mask != nullptr, mask_dtype, dM, [&](auto img, auto msk) {
+    return emphysema_typed(ctx, img, msk, vol, sigmas, n_sigmas, dout, layout);
+  });
 }
 
 // =====================================================================================
@@ -1059,7 +1097,7 @@ static int eig_batch(ife_ctx *ctx, const float *A6, int64_t n, float *outv, int 
   int rc = bind(ctx);
   if (rc) return rc;
   if (n < 0 || (n > 0 && (!A6 || !outv))) return fail(ctx, IFE_E_ARG, "null pointer");
-  if (mem != IFE_MEM_HOST && mem != IFE_MEM_DEVICE) return fail(ctx, IFE_E_ARG, "bad mem");
+  if ((rc = check_mem(ctx, mem))) return rc;
   if (n == 0) return IFE_OK;
   const void *dA;
   void *dO;
@@ -1118,9 +1156,9 @@ int ife_normalized_gaussian_convolution(ife_ctx *ctx, const float *image,
   int rc = bind(ctx);
   if (rc) return rc;
   if ((rc = check_vol(ctx, vol, true))) return rc;
-  if (mem != IFE_MEM_HOST && mem != IFE_MEM_DEVICE) return fail(ctx, IFE_E_ARG, "bad mem");
+  if ((rc = check_mem(ctx, mem))) return rc;
   if (!image || !certainty || !out) return fail(ctx, IFE_E_ARG, "null pointer");
-  if (!(sigma > 0.0)) return fail(ctx, IFE_E_ARG, "sigma must be positive");
+  if ((rc = check_sigma(ctx, sigma))) return rc;
   if ((rc = ife_ctx_reserve(ctx, vol))) return rc;
   const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
   const void *dI, *dC;
@@ -1153,10 +1191,10 @@ int ife_differential_normalized_convolution(ife_ctx *ctx, const float *image,
   int rc = bind(ctx);
   if (rc) return rc;
   if ((rc = check_vol(ctx, vol, true))) return rc;
-  if (mem != IFE_MEM_HOST && mem != IFE_MEM_DEVICE) return fail(ctx, IFE_E_ARG, "bad mem");
+  if ((rc = check_mem(ctx, mem))) return rc;
   if (!image || !certainty || !out) return fail(ctx, IFE_E_ARG, "null pointer");
-  if (!(sigma > 0.0)) return fail(ctx, IFE_E_ARG, "sigma must be positive");
-  if (axis < 0 || axis > 2) return fail(ctx, IFE_E_ARG, "axis must be 0 (x), 1 (y) or 2 (z)");
+  if ((rc = check_sigma(ctx, sigma))) return rc;
+  if ((rc = check_axis(ctx, axis))) return rc;
   if ((rc = ensure_slots(ctx, vol, 2))) return rc;
   const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
   const void *dI, *dC;
@@ -1204,38 +1242,14 @@ int ife_emphysema_features(ife_ctx *ctx, const void *image, int image_dtype, con
                            int n_sigmas, float *out, int layout, int mem) {
   int rc = bind(ctx);
   if (rc) return rc;
-  if ((rc = check_vol(ctx, vol, true))) return rc;
-  if ((rc = check_layout_mem(ctx, layout, mem))) return rc;
-  if (!image || !out || !sigmas) return fail(ctx, IFE_E_ARG, "null pointer");
-  if (n_sigmas < 1) return fail(ctx, IFE_E_ARG, "at least one sigma is required");
-  for (int s = 0; s < n_sigmas; ++s)
-    if (!(sigmas[s] > 0.0f)) return fail(ctx, IFE_E_ARG, "sigma[%d] must be positive", s);
-  if (image_dtype != IFE_F32 && image_dtype != IFE_I16)
-    return fail(ctx, IFE_E_ARG, "image dtype must be IFE_F32 or IFE_I16");
-  if (mask && mask_dtype != IFE_U8 && mask_dtype != IFE_U16)
-    return fail(ctx, IFE_E_ARG, "mask dtype must be IFE_U8 or IFE_U16");
-  if ((rc = ife_ctx_reserve(ctx, vol))) return rc;
-  const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
-  const size_t out_bytes = n * IFE_NUM_FEATURES * 4 * (size_t)n_sigmas;
-  const void *dI, *dM;
-  void *dO;
-  if ((rc = stage_in(ctx, mem, image, n * dtype_size(image_dtype), ctx->st_img, &dI))) return rc;
-  if ((rc = stage_in(ctx, mem, mask, n * (mask ? dtype_size(mask_dtype) : 0), ctx->st_mask, &dM)))
+  if ((rc = emphysema_check(ctx, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, out != nullptr,
+                            layout, mem)))
     return rc;
+  if ((rc = ife_ctx_reserve(ctx, vol))) return rc;
+  const size_t out_bytes = (size_t)(vol->nx * vol->ny * vol->nz) * IFE_NUM_FEATURES * 4 * (size_t)n_sigmas;
+  void *dO;
   if ((rc = stage_out_begin(ctx, mem, out, out_bytes, &dO))) return rc;
-  float *dout = (float *)dO;
-  const bool u16 = mask && mask_dtype == IFE_U16;
-  if (image_dtype == IFE_F32) {
-    rc = u16 ? emphysema_typed(ctx, (const float *)dI, (const uint16_t *)dM, vol, sigmas, n_sigmas,
-                               dout, layout)
-             : emphysema_typed(ctx, (const float *)dI, (const uint8_t *)dM, vol, sigmas, n_sigmas,
-                               dout, layout);
-  } else {
-    rc = u16 ? emphysema_typed(ctx, (const int16_t *)dI, (const uint16_t *)dM, vol, sigmas,
-                               n_sigmas, dout, layout)
-             : emphysema_typed(ctx, (const int16_t *)dI, (const uint8_t *)dM, vol, sigmas,
-                               n_sigmas, dout, layout);
-  }
+  rc = emphysema_staged(ctx, mem, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, (float *)dO, layout);
   if (rc) return rc;
   return stage_out_end(ctx, mem, out, out_bytes);
 }
@@ -1262,47 +1276,22 @@ int ife_emphysema_features_begin(ife_ctx *ctx, const void *image, int image_dtyp
                                  int n_sigmas, int layout) {
   int rc = bind(ctx);
   if (rc) return rc;
-  if ((rc = check_vol(ctx, vol, true))) return rc;
-  if ((rc = check_layout_mem(ctx, layout, IFE_MEM_HOST))) return rc;
-  if (!image || !sigmas) return fail(ctx, IFE_E_ARG, "null pointer");
-  if (n_sigmas < 1) return fail(ctx, IFE_E_ARG, "at least one sigma is required");
-  for (int s = 0; s < n_sigmas; ++s)
-    if (!(sigmas[s] > 0.0f)) return fail(ctx, IFE_E_ARG, "sigma[%d] must be positive", s);
-  if (image_dtype != IFE_F32 && image_dtype != IFE_I16)
-    return fail(ctx, IFE_E_ARG, "image dtype must be IFE_F32 or IFE_I16");
-  if (mask && mask_dtype != IFE_U8 && mask_dtype != IFE_U16)
-    return fail(ctx, IFE_E_ARG, "mask dtype must be IFE_U8 or IFE_U16");
+  if ((rc = emphysema_check(ctx, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, true, layout,
+                            IFE_MEM_HOST)))
+    return rc;
   if ((rc = ife_emphysema_features_end(ctx))) return rc;  // drop an earlier, unfinished run
   if ((rc = ife_ctx_reserve(ctx, vol))) return rc;
-  const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
-  ctx->sc_scale_bytes = n * IFE_NUM_FEATURES * sizeof(float);
+  ctx->sc_scale_bytes = (size_t)(vol->nx * vol->ny * vol->nz) * IFE_NUM_FEATURES * sizeof(float);
   if ((rc = ensure(ctx, ctx->sc_out, ctx->sc_scale_bytes * (size_t)n_sigmas))) return rc;
   if (!ctx->sc_copy) IFE_HIP(ctx, hipStreamCreateWithFlags(&ctx->sc_copy, hipStreamNonBlocking));
-  const void *dI, *dM;
-  if ((rc = stage_in(ctx, IFE_MEM_HOST, image, n * dtype_size(image_dtype), ctx->st_img, &dI))) return rc;
-  if ((rc = stage_in(ctx, IFE_MEM_HOST, mask, n * (mask ? dtype_size(mask_dtype) : 0), ctx->st_mask, &dM))) {
-    (void)hipStreamSynchronize(ctx->stream);  // the image upload may still read the caller's memory
-    return rc;
-  }
-  // From page-locked memory the uploads run asynchronously to the host: the caller may reuse
-  // image and mask once _begin returns, so it waits for them (not for the scales) before returning.
+  // The caller may reuse image and mask once _begin returns, so it waits for the uploads (not for
+  // the scales) before returning.
   hipEvent_t uploaded = nullptr;
-  if (hipEventCreateWithFlags(&uploaded, hipEventDisableTiming) != hipSuccess ||
-      hipEventRecord(uploaded, ctx->stream) != hipSuccess) {
-    if (uploaded) (void)hipEventDestroy(uploaded);
-    (void)hipStreamSynchronize(ctx->stream);
-    return fail(ctx, IFE_E_HIP, "upload event: %s", hipGetErrorString(hipGetLastError()));
-  }
-  float *dout = (float *)ctx->sc_out.p;
-  const bool u16 = mask && mask_dtype == IFE_U16;
   ctx->scale_events = &ctx->sc_done;
-  if (image_dtype == IFE_F32)
-    rc = u16 ? emphysema_typed(ctx, (const float *)dI, (const uint16_t *)dM, vol, sigmas, n_sigmas, dout, layout)
-             : emphysema_typed(ctx, (const float *)dI, (const uint8_t *)dM, vol, sigmas, n_sigmas, dout, layout);
-  else
-    rc = u16 ? emphysema_typed(ctx, (const int16_t *)dI, (const uint16_t *)dM, vol, sigmas, n_sigmas, dout, layout)
-             : emphysema_typed(ctx, (const int16_t *)dI, (const uint8_t *)dM, vol, sigmas, n_sigmas, dout, layout);
+  rc = emphysema_staged(ctx, IFE_MEM_HOST, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas,
+                        (float *)ctx->sc_out.p, layout, &uploaded);
   ctx->scale_events = nullptr;
+  if (!uploaded) return rc;  // stopped before the scales
   const hipError_t up = hipEventSynchronize(uploaded);
   (void)hipEventDestroy(uploaded);
   if (!rc && up != hipSuccess) rc = fail(ctx, IFE_E_HIP, "upload: %s", hipGetErrorString(up));
@@ -1333,10 +1322,8 @@ int ife_fd_hessian_features(ife_ctx *ctx, const void *image, int image_dtype, co
   if ((rc = check_vol(ctx, vol, false))) return rc;
   if ((rc = check_layout_mem(ctx, layout, mem))) return rc;
   if (!image || !out6) return fail(ctx, IFE_E_ARG, "null pointer");
-  if (image_dtype != IFE_F32 && image_dtype != IFE_I16)
-    return fail(ctx, IFE_E_ARG, "image dtype must be IFE_F32 or IFE_I16");
-  if (mask && mask_dtype != IFE_U8 && mask_dtype != IFE_U16)
-    return fail(ctx, IFE_E_ARG, "mask dtype must be IFE_U8 or IFE_U16");
+  if ((rc = check_image_dtype(ctx, image_dtype))) return rc;
+  if ((rc = check_mask_dtype(ctx, mask, mask_dtype, true))) return rc;
   const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
   const void *dI, *dM;
   void *dO;
@@ -1344,18 +1331,10 @@ int ife_fd_hessian_features(ife_ctx *ctx, const void *image, int image_dtype, co
   if ((rc = stage_in(ctx, mem, mask, n * (mask ? dtype_size(mask_dtype) : 0), ctx->st_mask, &dM)))
     return rc;
   if ((rc = stage_out_begin(ctx, mem, out6, n * 24, &dO))) return rc;
-  const bool u16 = mask && mask_dtype == IFE_U16;
-  if (image_dtype == IFE_F32) {
-    rc = u16 ? launch_features<FEAT_EIG6>(ctx, ValRaw<float>{(const float *)dI},
-                                          (const uint16_t *)dM, (float *)dO, vol, layout)
-             : launch_features<FEAT_EIG6>(ctx, ValRaw<float>{(const float *)dI},
-                                          (const uint8_t *)dM, (float *)dO, vol, layout);
-  } else {
-    rc = u16 ? launch_features<FEAT_EIG6>(ctx, ValRaw<int16_t>{(const int16_t *)dI},
-                                          (const uint16_t *)dM, (float *)dO, vol, layout)
-             : launch_features<FEAT_EIG6>(ctx, ValRaw<int16_t>{(const int16_t *)dI},
-                                          (const uint8_t *)dM, (float *)dO, vol, layout);
-  }
+  rc = with_types(image_dtype, dI, mask != nullptr, mask_dtype, dM, [&](auto img, auto msk) {
+    using TI = std::remove_cv_t<std::remove_pointer_t<decltype(img)>>;
+    return launch_features<FEAT_EIG6>(ctx, ValRaw<TI>{img}, msk, (float *)dO, vol, layout);
+  });
   if (rc) return rc;
   return stage_out_end(ctx, mem, out6, n * 24);
 }
@@ -1366,7 +1345,7 @@ int ife_fd_gradient_features(ife_ctx *ctx, const float *image, const float *mask
   int rc = bind(ctx);
   if (rc) return rc;
   if ((rc = check_vol(ctx, vol, false))) return rc;
-  if (mem != IFE_MEM_HOST && mem != IFE_MEM_DEVICE) return fail(ctx, IFE_E_ARG, "bad mem");
+  if ((rc = check_mem(ctx, mem))) return rc;
   if (!image || !out) return fail(ctx, IFE_E_ARG, "null pointer");
   const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
   const void *dI, *dM;
@@ -1386,7 +1365,7 @@ int ife_mask_image_f64(ife_ctx *ctx, const double *image, const double *mask, do
   int rc = bind(ctx);
   if (rc) return rc;
   if (n < 0 || (n > 0 && (!image || !mask || !out))) return fail(ctx, IFE_E_ARG, "null pointer");
-  if (mem != IFE_MEM_HOST && mem != IFE_MEM_DEVICE) return fail(ctx, IFE_E_ARG, "bad mem");
+  if ((rc = check_mem(ctx, mem))) return rc;
   if (n == 0) return IFE_OK;
   const void *dI, *dM;
   void *dO;
@@ -1411,20 +1390,14 @@ int ife_stage_prepare(ife_ctx *ctx, const void *image, int image_dtype, const vo
   if (rc) return rc;
   if ((rc = check_vol(ctx, slab, false))) return rc;
   if (!image || !tc) return fail(ctx, IFE_E_ARG, "null pointer");
-  if (image_dtype != IFE_F32 && image_dtype != IFE_I16)
-    return fail(ctx, IFE_E_ARG, "image dtype must be IFE_F32 or IFE_I16");
-  if (mask && mask_dtype != IFE_U8 && mask_dtype != IFE_U16)
-    return fail(ctx, IFE_E_ARG, "mask dtype must be IFE_U8 or IFE_U16");
+  if ((rc = check_image_dtype(ctx, image_dtype))) return rc;
+  if ((rc = check_mask_dtype(ctx, mask, mask_dtype, true))) return rc;
   if (y_chunks < 1 || slab->ny % y_chunks)
     return fail(ctx, IFE_E_SIZE, "ny must be a multiple of the number of Y chunks");
   const int64_t n = slab->nx * slab->ny * slab->nz;
   const PrepGeom pg{slab->nx, slab->ny, slab->nz, y_chunks, slab->ny / y_chunks};
-  const bool u16 = mask && mask_dtype == IFE_U16;
-  if (image_dtype == IFE_F32)
-    return u16 ? launch_prep(ctx, (const float *)image, (const uint16_t *)mask, tc, cf, n, pg)
-               : launch_prep(ctx, (const float *)image, (const uint8_t *)mask, tc, cf, n, pg);
-  return u16 ? launch_prep(ctx, (const int16_t *)image, (const uint16_t *)mask, tc, cf, n, pg)
-             : launch_prep(ctx, (const int16_t *)image, (const uint8_t *)mask, tc, cf, n, pg);
+  return with_types(image_dtype, image, mask != nullptr, mask_dtype, mask,
+                    [&](auto img, auto msk) { return launch_prep(ctx, img, msk, tc, cf, n, pg); });
 }
 
 int ife_stage_recursive_gaussian(ife_ctx *ctx, const float *in, float *out,
@@ -1434,12 +1407,9 @@ int ife_stage_recursive_gaussian(ife_ctx *ctx, const float *in, float *out,
   if ((rc = check_vol(ctx, vol, false))) return rc;
   if (!in || !out) return fail(ctx, IFE_E_ARG, "null pointer");
   if (in == out) return fail(ctx, IFE_E_ARG, "the axis pass is not in place");
-  if (axis < 0 || axis > 2) return fail(ctx, IFE_E_ARG, "axis must be 0 (x), 1 (y) or 2 (z)");
-  if (!(sigma > 0.0)) return fail(ctx, IFE_E_ARG, "sigma must be positive");
-  const int64_t len = axis == 0 ? vol->nx : axis == 1 ? vol->ny : vol->nz;
-  if (len < 4)
-    return fail(ctx, IFE_E_SIZE, "the recursive Gaussian needs at least 4 voxels along axis %d",
-                axis);
+  if ((rc = check_axis(ctx, axis))) return rc;
+  if ((rc = check_sigma(ctx, sigma))) return rc;
+  if ((rc = check_axis_len(ctx, vol, axis))) return rc;
   const float *ins[1] = {in};
   float *outs[1] = {out};
   return launch_iir(ctx, vol, axis, 1, ins, outs, &sigma);
@@ -1452,13 +1422,10 @@ int ife_stage_recursive_gaussian_batch(ife_ctx *ctx, int njobs, const float *con
   if (rc) return rc;
   if ((rc = check_vol(ctx, vol, false))) return rc;
   if (!in || !out || !sigmas) return fail(ctx, IFE_E_ARG, "null pointer");
-  if (axis < 0 || axis > 2) return fail(ctx, IFE_E_ARG, "axis must be 0 (x), 1 (y) or 2 (z)");
+  if ((rc = check_axis(ctx, axis))) return rc;
   for (int j = 0; j < njobs; ++j)
-    if (!(sigmas[j] > 0.0)) return fail(ctx, IFE_E_ARG, "sigma must be positive");
-  const int64_t len = axis == 0 ? vol->nx : axis == 1 ? vol->ny : vol->nz;
-  if (len < 4)
-    return fail(ctx, IFE_E_SIZE, "the recursive Gaussian needs at least 4 voxels along axis %d",
-                axis);
+    if ((rc = check_sigma(ctx, sigmas[j]))) return rc;
+  if ((rc = check_axis_len(ctx, vol, axis))) return rc;
   return launch_iir(ctx, vol, axis, njobs, in, out, sigmas, in_y_chunks);
 }
 
@@ -1511,9 +1478,8 @@ int ife_stage_recursive_gaussian_quotient(ife_ctx *ctx, int njobs, const float *
   if (!num || !den || !out || !sigmas) return fail(ctx, IFE_E_ARG, "null pointer");
   if (axis != 1 && axis != 2) return fail(ctx, IFE_E_ARG, "the quotient form runs on the strided axes: 1 (y) or 2 (z)");
   for (int j = 0; j < njobs; ++j)
-    if (!(sigmas[j] > 0.0)) return fail(ctx, IFE_E_ARG, "sigma must be positive");
-  if ((axis == 1 ? vol->ny : vol->nz) < 4)
-    return fail(ctx, IFE_E_SIZE, "the recursive Gaussian needs at least 4 voxels along axis %d", axis);
+    if ((rc = check_sigma(ctx, sigmas[j]))) return rc;
+  if ((rc = check_axis_len(ctx, vol, axis))) return rc;
   return launch_iir(ctx, vol, axis, njobs, num, out, sigmas, 1, nullptr, den);
 }
 
@@ -1525,13 +1491,10 @@ int ife_stage_features(ife_ctx *ctx, const float *num, const float *den, const v
   if ((rc = check_vol(ctx, slab, false))) return rc;
   if ((rc = check_layout_mem(ctx, layout, IFE_MEM_DEVICE))) return rc;
   if (!num || !out) return fail(ctx, IFE_E_ARG, "null pointer");
-  if (mask && mask_dtype != IFE_U8 && mask_dtype != IFE_U16)
-    return fail(ctx, IFE_E_ARG, "mask dtype must be IFE_U8 or IFE_U16");
-  if (mask && mask_dtype == IFE_U16)
-    return launch_features<FEAT_FEATURES8>(ctx, ValSmooth{num, den}, (const uint16_t *)mask, out,
-                                           slab, layout, halo_lo, halo_hi);
-  return launch_features<FEAT_FEATURES8>(ctx, ValSmooth{num, den}, (const uint8_t *)mask, out,
-                                         slab, layout, halo_lo, halo_hi);
+  if ((rc = check_mask_dtype(ctx, mask, mask_dtype, true))) return rc;
+  return with_mask_type(mask != nullptr, mask_dtype, mask, [&](auto msk) {
+    return launch_features<FEAT_FEATURES8>(ctx, ValSmooth{num, den}, msk, out, slab, layout, halo_lo, halo_hi);
+  });
 }
 
 // ---- measurement ----------------------------------------------------------------------

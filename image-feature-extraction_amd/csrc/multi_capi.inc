@@ -210,21 +210,19 @@ namespace {
 int multi_run(ife_multi *m, const void *image, int image_dtype, const void *mask, int mask_dtype,
               const ife_volume_desc *vol, const float *sigmas, int n_sigmas, int layout) {
   if (!vol || !image || !sigmas) return mfail(m, IFE_E_ARG, "null pointer");
-  if (n_sigmas < 1) return mfail(m, IFE_E_ARG, "at least one sigma is required");
-  for (int s = 0; s < n_sigmas; ++s)
-    if (!(sigmas[s] > 0.0f)) return mfail(m, IFE_E_ARG, "sigma[%d] must be positive", s);
-  if (image_dtype != IFE_F32 && image_dtype != IFE_I16)
-    return mfail(m, IFE_E_ARG, "image dtype must be IFE_F32 or IFE_I16");
-  if (mask && mask_dtype != IFE_U8 && mask_dtype != IFE_U16)
-    return mfail(m, IFE_E_ARG, "mask dtype must be IFE_U8 or IFE_U16");
-  if (layout != IFE_INTERLEAVED && layout != IFE_PLANAR) return mfail(m, IFE_E_ARG, "bad layout %d", layout);
   const int W = (int)m->ranks.size();
   const int64_t nx = vol->nx, ny = vol->ny, nz = vol->nz;
+  // the shared checks report through the first rank's context
+  ife_ctx *c0 = m->ranks[0].bulk;
+  int rc;
+  if ((rc = check_sigmas(c0, sigmas, n_sigmas)) || (rc = check_image_dtype(c0, image_dtype)) ||
+      (rc = check_mask_dtype(c0, mask, mask_dtype, true)) || (rc = check_layout_mem(c0, layout, IFE_MEM_HOST)))
+    return mfail(m, rc, "%s", c0->err.c_str());
   if (nx < 4 || ny < 4 || nz < (int64_t)4 * W)
     return mfail(m, IFE_E_SIZE, "every Z-slab needs at least 4 planes and every axis 4 voxels "
                                 "(%lld x %lld x %lld over %d devices)",
                  (long long)nx, (long long)ny, (long long)nz, W);
-  if (!(vol->sx > 0.0) || !(vol->sy > 0.0) || !(vol->sz > 0.0)) return mfail(m, IFE_E_ARG, "spacing must be positive");
+  if ((rc = check_vol(c0, vol, false))) return mfail(m, rc, "%s", c0->err.c_str());  // spacing
   const int nf = mask ? 2 : 1, S = n_sigmas;
   const int64_t plane = nx * ny;
   const size_t isz = dtype_size(image_dtype), msz = mask ? dtype_size(mask_dtype) : 0;

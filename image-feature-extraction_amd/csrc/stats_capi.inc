@@ -189,14 +189,23 @@ int launch_roi_histograms(ife_ctx *ctx, const float *dF, int layout, int ncomp, 
   a.nedges = n_edges;
   ProfScope ps(ctx, KK_HIST);
   const dim3 grid((unsigned)n_rois, ROI_SPLIT);
-  if (mask_dtype == IFE_U16)
-    hipLaunchKernelGGL(roi_histogram_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, dF, (const uint16_t *)dM,
-                       dRois, dEdges, dCounts, a);
-  else
-    hipLaunchKernelGGL(roi_histogram_kernel<uint8_t>, grid, dim3(256), 0, ctx->stream, dF, (const uint8_t *)dM,
-                       dRois, dEdges, dCounts, a);
-  IFE_HIP(ctx, hipGetLastError());
-  return IFE_OK;
+  return with_mask_type(true, mask_dtype, dM, [&](auto msk) -> int {
+    using TM = std::remove_cv_t<std::remove_pointer_t<decltype(msk)>>;
+    hipLaunchKernelGGL(roi_histogram_kernel<TM>, grid, dim3(256), 0, ctx->stream, dF, msk, dRois, dEdges, dCounts, a);
+    IFE_HIP(ctx, hipGetLastError());
+    return IFE_OK;
+  });
+}
+
+// labels to {0, 1} (tool :147-152, MakeBag :236-244)
+int launch_clamp01(ife_ctx *ctx, const void *dM, int mask_dtype, uint8_t *clamp, int64_t nvox) {
+  const unsigned blocks = (unsigned)std::min<int64_t>((nvox + 255) / 256, 8192);
+  return with_mask_type(true, mask_dtype, dM, [&](auto msk) -> int {
+    using TM = std::remove_cv_t<std::remove_pointer_t<decltype(msk)>>;
+    hipLaunchKernelGGL(clamp01_kernel<TM>, dim3(blocks), dim3(256), 0, ctx->stream, msk, clamp, nvox);
+    IFE_HIP(ctx, hipGetLastError());
+    return IFE_OK;
+  });
 }
 
 int check_fg(ife_ctx *ctx, const uint32_t *fg, int n_fg, const void *idx) {
@@ -213,7 +222,7 @@ template <typename T>
 static int equalized_edges_typed(ife_ctx *ctx, const T *sorted, int64_t n, int nbins, T *edges, int mem) {
   int rc = bind(ctx);
   if (rc) return rc;
-  if (mem != IFE_MEM_HOST && mem != IFE_MEM_DEVICE) return fail(ctx, IFE_E_ARG, "bad mem %d", mem);
+  if ((rc = check_mem(ctx, mem))) return rc;
   if (n < 0) return fail(ctx, IFE_E_ARG, "Iterator first must come before iterator last");
   if (nbins < 1) return fail(ctx, IFE_E_ARG, "at least one bin is required");
   if (n < nbins) return edge_status_to_rc(ctx, 1, 0, n, nbins);
@@ -239,7 +248,7 @@ extern "C" {
 int ife_sort_f32(ife_ctx *ctx, const float *in, int64_t n, float *out, int mem) {
   int rc = bind(ctx);
   if (rc) return rc;
-  if (mem != IFE_MEM_HOST && mem != IFE_MEM_DEVICE) return fail(ctx, IFE_E_ARG, "bad mem %d", mem);
+  if ((rc = check_mem(ctx, mem))) return rc;
   if (n < 0 || (n > 0 && (!in || !out))) return fail(ctx, IFE_E_ARG, "null pointer");
   if (n == 0) return IFE_OK;
   void *dO;
@@ -268,7 +277,7 @@ int ife_dense_histogram_f32(ife_ctx *ctx, const float *edges, int n_edges, const
                             int64_t n, uint32_t *counts, int mem) {
   int rc = bind(ctx);
   if (rc) return rc;
-  if (mem != IFE_MEM_HOST && mem != IFE_MEM_DEVICE) return fail(ctx, IFE_E_ARG, "bad mem %d", mem);
+  if ((rc = check_mem(ctx, mem))) return rc;
   if (!edges || !counts || (n > 0 && !values)) return fail(ctx, IFE_E_ARG, "null pointer");
   if (n_edges < 1 || n_edges > HIST_MAX_EDGES)
     return fail(ctx, IFE_E_ARG, "between 1 and %d edges are required", HIST_MAX_EDGES);
@@ -298,7 +307,7 @@ int ife_roi_histograms(ife_ctx *ctx, const float *features, int layout, int ncom
   if ((rc = check_vol(ctx, vol, false))) return rc;
   if ((rc = check_layout_mem(ctx, layout, mem))) return rc;
   if (!features || !mask || !edges || !counts) return fail(ctx, IFE_E_ARG, "null pointer");
-  if (mask_dtype != IFE_U8 && mask_dtype != IFE_U16) return fail(ctx, IFE_E_ARG, "mask dtype must be IFE_U8 or IFE_U16");
+  if ((rc = check_mask_dtype(ctx, mask, mask_dtype, false))) return rc;
   if (ncomp < 1 || n_edges < 1 || (int64_t)ncomp * (2 * n_edges + 1) > ROI_MAX_LDS_WORDS)
     return fail(ctx, IFE_E_ARG, "ncomp * (2 * n_edges + 1) must be between 3 and %d", ROI_MAX_LDS_WORDS);
   if (mem == IFE_MEM_HOST && (rc = check_rois(ctx, vol, rois, n_rois))) return rc;
@@ -337,11 +346,11 @@ int ife_bag_image(ife_ctx *ctx, const void *image, int image_dtype, const void *
   int rc = bind(ctx);
   if (rc) return rc;
   if ((rc = check_vol(ctx, vol, true))) return rc;
-  if (mem != IFE_MEM_HOST && mem != IFE_MEM_DEVICE) return fail(ctx, IFE_E_ARG, "bad mem %d", mem);
+  if ((rc = check_mem(ctx, mem))) return rc;
   if (!image || !mask || !sigmas || !edges || !counts) return fail(ctx, IFE_E_ARG, "null pointer");
-  if (n_sigmas < 1) return fail(ctx, IFE_E_ARG, "at least one sigma is required");
-  if (image_dtype != IFE_F32 && image_dtype != IFE_I16) return fail(ctx, IFE_E_ARG, "image dtype must be IFE_F32 or IFE_I16");
-  if (mask_dtype != IFE_U8 && mask_dtype != IFE_U16) return fail(ctx, IFE_E_ARG, "mask dtype must be IFE_U8 or IFE_U16");
+  if ((rc = check_sigmas(ctx, sigmas, n_sigmas))) return rc;
+  if ((rc = check_image_dtype(ctx, image_dtype))) return rc;
+  if ((rc = check_mask_dtype(ctx, mask, mask_dtype, false))) return rc;
   if (n_edges < 1 || (int64_t)IFE_NUM_FEATURES * (2 * n_edges + 1) > ROI_MAX_LDS_WORDS)
     return fail(ctx, IFE_E_ARG, "between 1 and %d edges per histogram", (ROI_MAX_LDS_WORDS / IFE_NUM_FEATURES - 1) / 2);
   if ((rc = check_rois(ctx, vol, rois, n_rois))) return rc;  // rois, edges and counts are host arrays
@@ -360,14 +369,7 @@ int ife_bag_image(ife_ctx *ctx, const void *image, int image_dtype, const void *
   IFE_HIP(ctx, hipMemsetAsync(ws + off_c, 0, cb, ctx->stream));
   uint8_t *clamp = (uint8_t *)(ws + off_m);
   float *feat = (float *)(ws + off_f);
-  {
-    const unsigned blocks = (unsigned)std::min<int64_t>(((int64_t)nvox + 255) / 256, 8192);
-    if (mask_dtype == IFE_U16)
-      hipLaunchKernelGGL(clamp01_kernel<uint16_t>, dim3(blocks), dim3(256), 0, ctx->stream, (const uint16_t *)dM, clamp, (int64_t)nvox);
-    else
-      hipLaunchKernelGGL(clamp01_kernel<uint8_t>, dim3(blocks), dim3(256), 0, ctx->stream, (const uint8_t *)dM, clamp, (int64_t)nvox);
-    IFE_HIP(ctx, hipGetLastError());
-  }
+  if ((rc = launch_clamp01(ctx, dM, mask_dtype, clamp, (int64_t)nvox))) return rc;
   if ((rc = ife_emphysema_features(ctx, dI, image_dtype, clamp, IFE_U8, vol, sigmas, n_sigmas, feat, IFE_PLANAR,
                                    IFE_MEM_DEVICE)))
     return rc;
@@ -450,8 +452,8 @@ int ife_samples_add_features(ife_ctx *ctx, ife_samples *s, int first_column, con
     if (mem == IFE_MEM_HOST)
       for (int64_t k = 0; k < n_indices; ++k)
         if (indices[k] < 0 || indices[k] >= nvox) return fail(ctx, IFE_E_ARG, "voxel index out of range");
-  } else if (mask_dtype != IFE_U8 && mask_dtype != IFE_U16) {
-    return fail(ctx, IFE_E_ARG, "mask dtype must be IFE_U8 or IFE_U16");
+  } else if ((rc = check_mask_dtype(ctx, mask, mask_dtype, false))) {
+    return rc;
   }
   const void *dF, *dM = nullptr, *dI = nullptr;
   if ((rc = stage_in(ctx, mem, features, (size_t)nvox * ncomp * 4, ctx->st_img, &dF))) return rc;
@@ -460,11 +462,10 @@ int ife_samples_add_features(ife_ctx *ctx, ife_samples *s, int first_column, con
   } else if ((rc = stage_in(ctx, mem, mask, (size_t)nvox * dtype_size(mask_dtype), ctx->st_mask, &dM))) {
     return rc;
   }
-  if (!indices && mask_dtype == IFE_U16)
-    return add_features_typed(ctx, s, first_column, (const float *)dF, layout, ncomp, (const uint16_t *)dM,
-                              nvox, foreground, n_foreground, nullptr, 0);
-  return add_features_typed(ctx, s, first_column, (const float *)dF, layout, ncomp, (const uint8_t *)dM, nvox,
-                            foreground, n_foreground, (const int64_t *)dI, n_indices);
+  return with_mask_type(!indices, mask_dtype, dM, [&](auto msk) {  // the indexed form reads no mask
+    return add_features_typed(ctx, s, first_column, (const float *)dF, layout, ncomp, msk, nvox, foreground,
+                              n_foreground, (const int64_t *)dI, n_indices);
+  });
 }
 
 // one image of the tool's loop (:176-265): clamp the labels to {0,1} (:147-152), a5 at
@@ -478,15 +479,14 @@ int ife_samples_add_image(ife_ctx *ctx, ife_samples *s, const void *image, int i
   if (rc) return rc;
   if (!s || s->ctx != ctx) return fail(ctx, IFE_E_ARG, "samples object does not belong to this context");
   if ((rc = check_vol(ctx, vol, true))) return rc;
-  if (mem != IFE_MEM_HOST && mem != IFE_MEM_DEVICE) return fail(ctx, IFE_E_ARG, "bad mem %d", mem);
+  if ((rc = check_mem(ctx, mem))) return rc;
   if (!image || !mask || !sigmas) return fail(ctx, IFE_E_ARG, "null pointer");
   if (n_sigmas < 1 || n_sigmas * IFE_NUM_FEATURES != s->ncol)
     return fail(ctx, IFE_E_ARG, "the samples object has %d columns, %d scales need %d", s->ncol, n_sigmas,
                 n_sigmas * IFE_NUM_FEATURES);
-  if (image_dtype != IFE_F32 && image_dtype != IFE_I16)
-    return fail(ctx, IFE_E_ARG, "image dtype must be IFE_F32 or IFE_I16");
-  if (mask_dtype != IFE_U8 && mask_dtype != IFE_U16)
-    return fail(ctx, IFE_E_ARG, "mask dtype must be IFE_U8 or IFE_U16");
+  if ((rc = check_sigmas(ctx, sigmas, n_sigmas))) return rc;
+  if ((rc = check_image_dtype(ctx, image_dtype))) return rc;
+  if ((rc = check_mask_dtype(ctx, mask, mask_dtype, false))) return rc;
   if ((rc = check_fg(ctx, foreground, n_foreground, indices))) return rc;
   const int64_t nvox = vol->nx * vol->ny * vol->nz;
   if (indices) {
@@ -501,16 +501,7 @@ int ife_samples_add_image(ife_ctx *ctx, ife_samples *s, const void *image, int i
   if (indices && (rc = stage_in(ctx, mem, indices, (size_t)n_indices_per_scale * n_sigmas * 8, s->idx, &dIdx)))
     return rc;
   if ((rc = ensure(ctx, s->clamp, (size_t)nvox))) return rc;
-  {
-    const unsigned blocks = (unsigned)std::min<int64_t>((nvox + 255) / 256, 8192);
-    if (mask_dtype == IFE_U16)
-      hipLaunchKernelGGL(clamp01_kernel<uint16_t>, dim3(blocks), dim3(256), 0, ctx->stream,
-                         (const uint16_t *)dM, (uint8_t *)s->clamp.p, nvox);
-    else
-      hipLaunchKernelGGL(clamp01_kernel<uint8_t>, dim3(blocks), dim3(256), 0, ctx->stream,
-                         (const uint8_t *)dM, (uint8_t *)s->clamp.p, nvox);
-    IFE_HIP(ctx, hipGetLastError());
-  }
+  if ((rc = launch_clamp01(ctx, dM, mask_dtype, (uint8_t *)s->clamp.p, nvox))) return rc;
   if (!dIdx) {
     // all-foreground branch, fused: the feature kernel writes the eight features of every
     // sampled voxel straight into the columns (raster order); no feature volume exists
@@ -538,12 +529,12 @@ int ife_samples_add_image(ife_ctx *ctx, ife_samples *s, const void *image, int i
     {
       ProfScope ps(ctx, KK_GATHER);
       const unsigned sb = (unsigned)std::min<int64_t>((nseg + 3) / 4, 32768);
-      if (mask_dtype == IFE_U16)
-        hipLaunchKernelGGL(sample_code_kernel<uint16_t>, dim3(sb), dim3(256), 0, ctx->stream,
-                           (const uint16_t *)dM, code, segs, (int)vol->nx, gx, nseg, a);
-      else
-        hipLaunchKernelGGL(sample_code_kernel<uint8_t>, dim3(sb), dim3(256), 0, ctx->stream,
-                           (const uint8_t *)dM, code, segs, (int)vol->nx, gx, nseg, a);
+      with_mask_type(true, mask_dtype, dM, [&](auto msk) {
+        using TM = std::remove_cv_t<std::remove_pointer_t<decltype(msk)>>;
+        hipLaunchKernelGGL(sample_code_kernel<TM>, dim3(sb), dim3(256), 0, ctx->stream, msk, code, segs,
+                           (int)vol->nx, gx, nseg, a);
+        return IFE_OK;
+      });
       hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)nchunks), dim3(SORT_THREADS), 0, ctx->stream, segs, nseg, sums);
       hipLaunchKernelGGL(scan_chunks_kernel, dim3(1), dim3(SORT_THREADS), 0, ctx->stream, sums, (int)nchunks, ctr);
       hipLaunchKernelGGL(chunk_scan_kernel, dim3((unsigned)nchunks), dim3(SORT_THREADS), 0, ctx->stream, segs, nseg, sums);
@@ -561,10 +552,9 @@ int ife_samples_add_image(ife_ctx *ctx, ife_samples *s, const void *image, int i
     sink.columns = (float *)s->data.p;
     sink.stride = s->cap;
     sink.offset = have;
-    const uint8_t *cm = (const uint8_t *)s->clamp.p;
-    rc = image_dtype == IFE_F32
-             ? emphysema_typed(ctx, (const float *)dI, cm, vol, sigmas, n_sigmas, nullptr, IFE_PLANAR, &sink)
-             : emphysema_typed(ctx, (const int16_t *)dI, cm, vol, sigmas, n_sigmas, nullptr, IFE_PLANAR, &sink);
+    rc = with_types(image_dtype, dI, true, IFE_U8, s->clamp.p, [&](auto img, auto cm) {
+      return emphysema_typed(ctx, img, cm, vol, sigmas, n_sigmas, nullptr, IFE_PLANAR, &sink);
+    });
     if (rc) return rc;
     for (int c = 0; c < s->ncol; ++c) s->count[c] = have + (int64_t)h;
     s->sorted = false;
