@@ -32,6 +32,7 @@ OPT_FEAT_RING = 10
 Z_STATE_BYTES = 32   # IFE_Z_STATE_BYTES: one state record of the slab Z pass, per line and job
 Z_OVERLAP_LO, Z_OVERLAP_HI = 3, 4  # IFE_Z_OVERLAP_*: neighbour planes around a slab's input
 NUM_FEATURES = 8
+MAX_KERNEL_KINDS = 24  # IFE_MAX_KERNEL_KINDS
 FEATURE_NAMES = ("GaussianBlur", "GradientMagnitude", "Eigenvalue1", "Eigenvalue2",
                  "Eigenvalue3", "LaplacianOfGaussian", "GaussianCurvature", "FrobeniusNorm")
 
@@ -55,6 +56,7 @@ EXPORTS = (
     "ife_samples_create", "ife_samples_destroy", "ife_samples_count", "ife_samples_clear",
     "ife_samples_add_features", "ife_samples_add_image", "ife_samples_sort",
     "ife_samples_equalized_edges", "ife_samples_read_column",
+    "ife_signed_distance_map", "ife_expected_distance",
 )
 
 
@@ -167,6 +169,9 @@ def load_library():
     lib.ife_samples_sort.argtypes = [vp, vp]
     lib.ife_samples_equalized_edges.argtypes = [vp, vp, i32, vp]
     lib.ife_samples_read_column.argtypes = [vp, vp, i32, vp, i64]
+    lib.ife_signed_distance_map.argtypes = [vp, vp, i32, vd, i32, i32, vp, i32]
+    lib.ife_expected_distance.argtypes = [vp, vp, i32, vp, vd, C.POINTER(C.c_double),
+                                          C.POINTER(i64), i32]
     _lib = lib
     return lib
 
@@ -261,8 +266,8 @@ class Context:
         self._chk(self._lib.ife_ctx_synchronize(self._h))
 
     def kernel_times(self):
-        arr = (KernelTime * 16)()
-        n = self._chk(self._lib.ife_get_kernel_times(self._h, arr, 16))
+        arr = (KernelTime * MAX_KERNEL_KINDS)()
+        n = self._chk(self._lib.ife_get_kernel_times(self._h, arr, MAX_KERNEL_KINDS))
         return {arr[i].name.decode(): (int(arr[i].launches), float(arr[i].total_ms))
                 for i in range(n)}
 
@@ -397,7 +402,44 @@ class Context:
                                                MEM_HOST))
         return out
 
+    # ---- signed Maurer distance map, expected distance --------------------------
+    def signed_distance_map(self, mask, spacing=(1.0, 1.0, 1.0), inside_is_positive=True,
+                            squared=False):
+        """float64 [z, y, x]: distance to the six-neighbour contour of mask != 0, positive inside
+        (or outside); +-sqrt(DBL_MAX) (+-DBL_MAX squared) everywhere when there is no contour."""
+        if mask is None:
+            raise TypeError("a mask is required")
+        mask, mdt, mptr = _mask_arg(mask)
+        d = _desc(mask.shape, spacing)
+        out = np.empty(mask.shape, np.float64)
+        self._chk(self._lib.ife_signed_distance_map(
+            self._h, mptr, mdt, C.byref(d), int(bool(inside_is_positive)), int(bool(squared)),
+            out.ctypes.data, MEM_HOST))
+        return out
+
+    def expected_distance(self, mask, prob, spacing=(1.0, 1.0, 1.0)):
+        """(mean over mask != 0 of distance map * prob, number of voxels with mask != 0)."""
+        if mask is None:
+            raise TypeError("a mask is required")
+        mask, mdt, mptr = _mask_arg(mask)
+        prob = np.ascontiguousarray(prob, np.float64)
+        if prob.shape != mask.shape:
+            raise ValueError("mask and prob differ in shape")
+        d = _desc(mask.shape, spacing)
+        value, n = C.c_double(), C.c_int64()
+        self._chk(self._lib.ife_expected_distance(
+            self._h, mptr, mdt, prob.ctypes.data, C.byref(d), C.byref(value), C.byref(n), MEM_HOST))
+        return value.value, n.value
+
     # ---- device-pointer entry points (inputs already in HBM) ------------------
+    def signed_distance_map_device(self, mask_ptr, mask_dtype, shape_zyx, spacing, out_ptr,
+                                   inside_is_positive=True, squared=False):
+        """Enqueues on the context's stream; out_ptr: float64 [z, y, x] in device memory."""
+        d = _desc(shape_zyx, spacing)
+        self._chk(self._lib.ife_signed_distance_map(
+            self._h, C.c_void_p(mask_ptr or 0), mask_dtype, C.byref(d),
+            int(bool(inside_is_positive)), int(bool(squared)), C.c_void_p(out_ptr or 0), MEM_DEVICE))
+
     def emphysema_features_device(self, image_ptr, image_dtype, mask_ptr, mask_dtype, shape_zyx,
                                   spacing, sigmas, out_ptr, layout=INTERLEAVED):
         d = _desc(shape_zyx, spacing)

@@ -22,6 +22,7 @@
 #include "feature_kernels.hpp"
 #include "iir_types.hpp"
 #include "stats_kernels.hpp"
+#include "distance_kernels.hpp"
 #define IFE_IIR_NS iir_exact
 #define IFE_IIR_FMA 0
 #include "iir_kernels.inc"
@@ -84,11 +85,17 @@ enum KernelKind {
   KK_GATHER,
   KK_EDGES,
   KK_HIST,
+  KK_EDT_X,
+  KK_EDT_Y,
+  KK_EDT_Z,
+  KK_EDT_REDUCE,
   KK_COUNT
 };
+static_assert(KK_COUNT <= IFE_MAX_KERNEL_KINDS, "ife_get_kernel_times callers size their arrays by IFE_MAX_KERNEL_KINDS");
 const char *kKindNames[KK_COUNT] = {"iir_z", "iir_x", "iir_y", "zslab_sweep", "zslab_combine", "features", "eig_batch",
                                     "divide", "mask_f64", "prep", "sort_hist", "sort_scan",
-                                    "sort_scatter", "gather", "edges", "dense_histogram"};
+                                    "sort_scatter", "gather", "edges", "dense_histogram", "edt_x", "edt_y",
+                                    "edt_z", "edt_reduce"};
 
 struct DevBuf {
   void *p = nullptr;
@@ -126,6 +133,9 @@ struct ife_ctx {
   DevBuf pre[2];  // image*certainty and certainty as float (prepass, shared by all scales)
   DevBuf ck_y[IIR_MAX_JOBS], ck_x[IIR_MAX_JOBS];  // one checkpoint area per concurrent job
   DevBuf st_img, st_mask, st_aux, st_out;  // HOST-mode staging
+  // distance map: candidate stacks of the line passes (values, indices), the squared map and
+  // the per-line partial sums of the expected distance
+  DevBuf edt_g, edt_i, edt_d2, edt_part;
   // streaming form of the scale loop (ife_emphysema_features_begin / _fetch / _end)
   DevBuf sc_out;                     // all scales, device resident
   std::vector<hipEvent_t> sc_done;   // one per scale: its feature launch has finished
@@ -1008,7 +1018,8 @@ void ife_ctx_destroy(ife_ctx *ctx) {
   for (auto e : ctx->sc_done) (void)hipEventDestroy(e);
   if (ctx->sc_copy) (void)hipStreamDestroy(ctx->sc_copy);
   std::vector<DevBuf *> bufs = {&ctx->pre[0], &ctx->pre[1], &ctx->st_img, &ctx->st_mask,
-                                &ctx->st_aux, &ctx->st_out, &ctx->sc_out};
+                                &ctx->st_aux, &ctx->st_out, &ctx->sc_out, &ctx->edt_g,
+                                &ctx->edt_i, &ctx->edt_d2, &ctx->edt_part};
   for (auto &sl : ctx->fld)
     for (auto &b : sl) bufs.push_back(&b);
   for (auto &b : ctx->ck_y) bufs.push_back(&b);
@@ -1573,4 +1584,5 @@ int ife_reset_kernel_times(ife_ctx *ctx) {
 }  // extern "C"
 
 #include "stats_capi.inc"
+#include "distance_capi.inc"
 #include "multi_capi.inc"

@@ -449,9 +449,32 @@ int ife_samples_equalized_edges(ife_ctx *ctx, ife_samples *s, int nbins, float *
 int ife_samples_read_column(ife_ctx *ctx, const ife_samples *s, int column, float *out,
                             int64_t capacity);
 
+/* ---- signed distance map, expected distance ------------------------ */
+
+/* itk::SignedMaurerDistanceMapImageFilter<Image<TMask,3>, Image<double,3>> as wired at
+ * include/ife/Statistics/ExpectedDistanceFromCenterToInterestPoint.h:16-19 (BackgroundValue 0,
+ * UseImageSpacing on).  mask: IFE_U8 or IFE_U16, foreground = mask != 0; NULL is IFE_E_ARG.
+ * Sites are the foreground voxels with a background face neighbour inside the volume
+ * (BinaryContourImageFilter, FullyConnected off); D2(v) = min over sites c of
+ * ((hx(c)-hx(v))^2 + (hy(c)-hy(v))^2) + (hz(c)-hz(v))^2 with h(i) = (double)i * spacing, every
+ * operation rounded on its own; out = +-(squared ? D2 : sqrt(D2)), positive where
+ * (mask != 0) == (inside_is_positive != 0).  A volume without a site (all foreground or all
+ * background) gives D2 = DBL_MAX everywhere, as ITK leaves it; that is not an error.  Any axis
+ * length >= 1; nx <= 32768 (IFE_E_SIZE beyond).  `out` may not be NULL. */
+int ife_signed_distance_map(ife_ctx *ctx, const void *mask, int mask_dtype,
+                            const ife_volume_desc *vol, int inside_is_positive, int squared,
+                            double *out, int mem);
+/* expectedDistanceFromCenterToInterestPoint (same header, :9-43): the mean over the foreground
+ * of (unsquared, inside-positive map) * prob; 0 when the mask is empty (:41).  The map is not
+ * stored: the last pass feeds a reduction with a fixed partition and order (same input, same
+ * bits).  prob follows `mem`; result and n_inside (the number of foreground voxels; may be NULL)
+ * are HOST scalars; the call blocks. */
+int ife_expected_distance(ife_ctx *ctx, const void *mask, int mask_dtype, const double *prob,
+                          const ife_volume_desc *vol, double *result, int64_t *n_inside, int mem);
+
 /* ---- measurement ------------------------------------------------------------------- */
 
-#define IFE_MAX_KERNEL_KINDS 16
+#define IFE_MAX_KERNEL_KINDS 24
 typedef struct {
   char name[48];
   int64_t launches;
