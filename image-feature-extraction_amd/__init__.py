@@ -29,6 +29,7 @@ OPT_TRIG_MODE, OPT_DSCALE_MODE, OPT_PROFILE, OPT_ZCHUNK, OPT_IIR_BLOCK, OPT_IIR_
 OPT_FUSED_DIVIDE = 8
 OPT_CONST_LINES = 9
 OPT_FEAT_RING = 10
+OPT_DENSE_SCRATCH_MB = 11
 Z_STATE_BYTES = 32   # IFE_Z_STATE_BYTES: one state record of the slab Z pass, per line and job
 Z_OVERLAP_LO, Z_OVERLAP_HI = 3, 4  # IFE_Z_OVERLAP_*: neighbour planes around a slab's input
 NUM_FEATURES = 8
@@ -53,6 +54,7 @@ EXPORTS = (
     "ife_multi_emphysema_features", "ife_multi_emphysema_features_begin",
     "ife_multi_emphysema_features_fetch", "ife_multi_emphysema_features_end",
     "ife_sort_f32", "ife_equalized_edges_f32", "ife_equalized_edges_f64", "ife_dense_histogram_f32", "ife_roi_histograms", "ife_bag_image",
+    "ife_dense_rois", "ife_dense_roi_histograms", "ife_bag_image_dense",
     "ife_samples_create", "ife_samples_destroy", "ife_samples_count", "ife_samples_clear",
     "ife_samples_add_features", "ife_samples_add_image", "ife_samples_sort",
     "ife_samples_equalized_edges", "ife_samples_read_column",
@@ -157,6 +159,11 @@ def load_library():
     lib.ife_roi_histograms.argtypes = [vp, vp, i32, i32, vp, i32, vd, vp, i32, vp, i32, vp, i32]
     lib.ife_bag_image.argtypes = [vp, vp, i32, vp, i32, vd, C.POINTER(C.c_float), i32, vp, i32, vp,
                                   i32, vp, i32]
+    lib.ife_dense_rois.argtypes = [vp, vp, i32, vd, C.POINTER(i64), C.POINTER(i64), vp, i64, i32]
+    lib.ife_dense_roi_histograms.argtypes = [vp, vp, i32, i32, vp, i32, vp, i32, vd, C.POINTER(i64), vp,
+                                             i32, vp, i64, C.POINTER(i64), i32]
+    lib.ife_bag_image_dense.argtypes = [vp, vp, i32, vp, i32, vp, i32, vd, C.POINTER(C.c_float), i32,
+                                        C.POINTER(i64), vp, i32, vp, i64, C.POINTER(i64), i32]
     lib.ife_samples_create.argtypes = [vp, i32, C.POINTER(vp)]
     lib.ife_samples_destroy.argtypes = [vp]
     lib.ife_samples_destroy.restype = None
@@ -208,6 +215,11 @@ def _mask_arg(mask):
 
 def _sigma_arg(sigmas):
     return (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
+
+
+def _size_arg(size_xyz):
+    sx, sy, sz = (int(v) for v in size_xyz)
+    return (C.c_int64 * 3)(sx, sy, sz)
 
 
 def _ptr_array(ptrs):
@@ -584,6 +596,71 @@ class Context:
             rois.shape[0], edges.ctypes.data, ne,
             counts.ctypes.data, MEM_HOST))
         return counts
+
+    # ---- the dense bag: one region per mask voxel whose box fits ----------------------
+    def _dense_count(self, gen_mask, size_xyz, spacing=(1.0, 1.0, 1.0)):
+        """Number of regions of DenseROIGenerator(gen_mask).generate(size)."""
+        gen_mask, gdt, gptr = _mask_arg(gen_mask)
+        d = _desc(gen_mask.shape, spacing)
+        n = C.c_int64()
+        self._chk(self._lib.ife_dense_rois(self._h, gptr, gdt, C.byref(d), _size_arg(size_xyz),
+                                           C.byref(n), None, 0, MEM_HOST))
+        return n.value
+
+    def dense_rois(self, mask, size):
+        """Boxes (n, 6) int64 {x0, y0, z0, sx, sy, sz} around every voxel of mask != 0 whose box
+        of `size` = (sx, sy, sz) fits the volume, raster order."""
+        if mask is None:
+            raise TypeError("a mask is required")
+        n = self._dense_count(mask, size)
+        mask, mdt, mptr = _mask_arg(mask)
+        d = _desc(mask.shape, (1.0, 1.0, 1.0))
+        rois = np.empty((max(n, 1), 6), np.int64)
+        got = C.c_int64()
+        self._chk(self._lib.ife_dense_rois(self._h, mptr, mdt, C.byref(d), _size_arg(size),
+                                           C.byref(got), rois.ctypes.data, rois.shape[0], MEM_HOST))
+        return rois[:got.value]
+
+    def dense_roi_histograms(self, features, mask, size, edges, gen_mask=None,
+                             spacing=(1.0, 1.0, 1.0), layout=INTERLEAVED):
+        """ctx.roi_histograms for the boxes of ctx.dense_rois(gen_mask or mask, size), without the
+        boxes: counts (n_rois, ncomp, n_edges+1) uint32."""
+        if mask is None:
+            raise TypeError("a mask is required")
+        f = np.ascontiguousarray(features, np.float32)
+        n = self._dense_count(mask if gen_mask is None else gen_mask, size, spacing)
+        mask, mdt, mptr = _mask_arg(mask)
+        gen_mask, gdt, gptr = _mask_arg(gen_mask)
+        edges = np.ascontiguousarray(edges, np.float32)
+        ncomp, ne = edges.shape
+        d = _desc(mask.shape, spacing)
+        counts = np.empty((max(n, 1), ncomp, ne + 1), np.uint32)
+        got = C.c_int64()
+        self._chk(self._lib.ife_dense_roi_histograms(
+            self._h, f.ctypes.data, layout, ncomp, mptr, mdt, gptr, gdt, C.byref(d), _size_arg(size),
+            edges.ctypes.data, ne, counts.ctypes.data, counts.shape[0], C.byref(got), MEM_HOST))
+        return counts[:got.value]
+
+    def bag_image_dense(self, image, mask, sigmas, size, edges, gen_mask=None,
+                        spacing=(1.0, 1.0, 1.0)):
+        """One image of MakeBagDense: counts (n_rois, n_sigmas*8, n_edges+1) uint32."""
+        if mask is None:
+            raise TypeError("a mask is required")
+        image, idt = _image_arg(image)
+        n = self._dense_count(mask if gen_mask is None else gen_mask, size, spacing)
+        mask, mdt, mptr = _mask_arg(mask)
+        gen_mask, gdt, gptr = _mask_arg(gen_mask)
+        edges = np.ascontiguousarray(edges, np.float32)
+        ne = edges.shape[1]
+        d = _desc(image.shape, spacing)
+        sig = _sigma_arg(sigmas)
+        counts = np.empty((max(n, 1), 8 * len(sigmas), ne + 1), np.uint32)
+        got = C.c_int64()
+        self._chk(self._lib.ife_bag_image_dense(
+            self._h, image.ctypes.data, idt, mptr, mdt, gptr, gdt, C.byref(d), sig, len(sigmas),
+            _size_arg(size), edges.ctypes.data, ne, counts.ctypes.data, counts.shape[0],
+            C.byref(got), MEM_HOST))
+        return counts[:got.value]
 
     def samples(self, n_columns):
         return Samples(self, n_columns)

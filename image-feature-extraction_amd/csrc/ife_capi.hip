@@ -23,6 +23,7 @@
 #include "iir_types.hpp"
 #include "stats_kernels.hpp"
 #include "distance_kernels.hpp"
+#include "dense_kernels.hpp"
 #define IFE_IIR_NS iir_exact
 #define IFE_IIR_FMA 0
 #include "iir_kernels.inc"
@@ -89,13 +90,16 @@ enum KernelKind {
   KK_EDT_Y,
   KK_EDT_Z,
   KK_EDT_REDUCE,
+  KK_DENSE_CODE,
+  KK_DENSE_XY,
+  KK_DENSE_Z,
   KK_COUNT
 };
 static_assert(KK_COUNT <= IFE_MAX_KERNEL_KINDS, "ife_get_kernel_times callers size their arrays by IFE_MAX_KERNEL_KINDS");
 const char *kKindNames[KK_COUNT] = {"iir_z", "iir_x", "iir_y", "zslab_sweep", "zslab_combine", "features", "eig_batch",
                                     "divide", "mask_f64", "prep", "sort_hist", "sort_scan",
                                     "sort_scatter", "gather", "edges", "dense_histogram", "edt_x", "edt_y",
-                                    "edt_z", "edt_reduce"};
+                                    "edt_z", "edt_reduce", "dense_code", "dense_box_xy", "dense_box_z"};
 
 struct DevBuf {
   void *p = nullptr;
@@ -136,6 +140,9 @@ struct ife_ctx {
   // distance map: candidate stacks of the line passes (values, indices), the squared map and
   // the per-line partial sums of the expected distance
   DevBuf edt_g, edt_i, edt_d2, edt_part;
+  // dense bag: centre flags and numbers, the scratch of the box passes, clamped labels and features
+  DevBuf dn_centres, dn_ws, dn_feat;
+  int dense_scratch_mb = 0;  // IFE_OPT_DENSE_SCRATCH_MB: 0 = sized from the free device memory
   // streaming form of the scale loop (ife_emphysema_features_begin / _fetch / _end)
   DevBuf sc_out;                     // all scales, device resident
   std::vector<hipEvent_t> sc_done;   // one per scale: its feature launch has finished
@@ -1019,7 +1026,8 @@ void ife_ctx_destroy(ife_ctx *ctx) {
   if (ctx->sc_copy) (void)hipStreamDestroy(ctx->sc_copy);
   std::vector<DevBuf *> bufs = {&ctx->pre[0], &ctx->pre[1], &ctx->st_img, &ctx->st_mask,
                                 &ctx->st_aux, &ctx->st_out, &ctx->sc_out, &ctx->edt_g,
-                                &ctx->edt_i, &ctx->edt_d2, &ctx->edt_part};
+                                &ctx->edt_i, &ctx->edt_d2, &ctx->edt_part, &ctx->dn_centres,
+                                &ctx->dn_ws, &ctx->dn_feat};
   for (auto &sl : ctx->fld)
     for (auto &b : sl) bufs.push_back(&b);
   for (auto &b : ctx->ck_y) bufs.push_back(&b);
@@ -1074,6 +1082,10 @@ int ife_ctx_set_option(ife_ctx *ctx, int option, int value) {
       return IFE_OK;
     case IFE_OPT_FEAT_RING:
       ctx->feat_ring = value ? 1 : 0;
+      return IFE_OK;
+    case IFE_OPT_DENSE_SCRATCH_MB:
+      if (value < 0) return fail(ctx, IFE_E_ARG, "the dense scratch bound must be >= 0 MiB");
+      ctx->dense_scratch_mb = value;
       return IFE_OK;
     case IFE_OPT_IIR_BLOCK:
       if (value != 0 && value != 8 && value != 10 && value != 12 && value != 16)
@@ -1585,4 +1597,5 @@ int ife_reset_kernel_times(ife_ctx *ctx) {
 
 #include "stats_capi.inc"
 #include "distance_capi.inc"
+#include "dense_capi.inc"
 #include "multi_capi.inc"

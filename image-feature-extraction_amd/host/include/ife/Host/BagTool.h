@@ -8,9 +8,10 @@
 // drop the flags they do not read: MakeBagDense has no -r/-R/-n, MakeBagOnlyIntensity no -s).
 //
 // The features of all scales stay in HBM and the per-region histograms are counted there
-// (ife_bag_image; ife_roi_histograms on the image for the intensity variant); only the
-// counts come back.  Frequencies are formed as DenseHistogram::getFrequencies does
-// (DenseHistogram.h:55-60).
+// (ife_bag_image; ife_roi_histograms on the image for the intensity variant; for the dense
+// variant ife_bag_image_dense, which takes the generator's rule in place of the box list and
+// counts by sliding box sums); only the counts come back.  Frequencies are formed as
+// DenseHistogram::getFrequencies does (DenseHistogram.h:55-60).
 #ifndef IFE_HOST_BAGTOOL_H
 #define IFE_HOST_BAGTOOL_H
 
@@ -109,6 +110,11 @@ inline int bag_main(int argc, char *argv[], BagVariant variant, const char *tool
 
   // regions: from the file, or generated on the (binary) mask / the thresholded ROI mask
   std::vector<RegionType> rois;
+  MaskImageType::Pointer roiMask = MaskImageType::New();  // -M thresholded at -v; the dense call reads it too
+  SizeType roiSize;
+  roiSize[0] = roiSizeXArg.getValue();
+  roiSize[1] = roiSizeYArg.getValue();
+  roiSize[2] = roiSizeZArg.getValue();
   const ImageType *image = nullptr;
   const MaskImageType *mask = nullptr;
   try {
@@ -124,7 +130,6 @@ inline int bag_main(int argc, char *argv[], BagVariant variant, const char *tool
   }
   if (roiPath.empty()) {
     try {
-      MaskImageType::Pointer roiMask = MaskImageType::New();
       if (!roiMaskPath.empty()) {
         std::cout << "Using ROI mask." << std::endl;
         itk::ImageFileReader<MaskImageType>::Pointer roiMaskReader = itk::ImageFileReader<MaskImageType>::New();
@@ -137,10 +142,6 @@ inline int bag_main(int argc, char *argv[], BagVariant variant, const char *tool
           roiMask->GetBufferPointer()[v] = rm->GetBufferPointer()[v] == roiMaskValue ? 1 : 0;
       }
       const MaskImageType *genMask = roiMaskPath.empty() ? mask : roiMask.GetPointer();
-      SizeType roiSize;
-      roiSize[0] = roiSizeXArg.getValue();
-      roiSize[1] = roiSizeYArg.getValue();
-      roiSize[2] = roiSizeZArg.getValue();
       if (dense) rois = itk::DenseROIGenerator<MaskImageType>(genMask).generate(roiSize);
       else rois = itk::RegionOfInterestGenerator<MaskImageType>(genMask).generate(numROIs, roiSize);
       const std::string roiOutPath(Path::join(outDirPath, prefix + ".ROIInfo"));
@@ -218,17 +219,33 @@ inline int bag_main(int argc, char *argv[], BagVariant variant, const char *tool
   }
   const size_t totalBins = histSize * numHistograms;
 
-  // the bag: one row per region, histSize columns per (scale, feature)
+  // the bag: one row per region, histSize columns per (scale, feature).  The dense variant
+  // sends no boxes: the device applies the generator's rule itself.
   std::vector<int64_t> boxes;
-  for (const RegionType &roi : rois)
-    for (int k = 0; k < 6; ++k) boxes.push_back(k < 3 ? roi.GetIndex()[k] : (int64_t)roi.GetSize()[k - 3]);
+  if (!dense)
+    for (const RegionType &roi : rois)
+      for (int k = 0; k < 6; ++k) boxes.push_back(k < 3 ? roi.GetIndex()[k] : (int64_t)roi.GetSize()[k - 3]);
   std::vector<uint32_t> counts(rois.size() * totalBins);
   for (size_t i = 0; i < scales.size(); ++i) std::cout << "Processing scale " << scales[i] << std::endl;
   try {
     ife::host::Engine &engine = ife::host::Engine::Instance();
     const ife_volume_desc d = ife::host::describe(*image);
-    if (rois.size() > 0x7fffffff) throw itk::ExceptionObject("more than 2^31-1 regions", toolName);
-    if (!rois.empty() && intensity)  // the image itself is the one-component "feature volume"
+    if (!dense && rois.size() > 0x7fffffff) throw itk::ExceptionObject("more than 2^31-1 regions", toolName);
+    if (!rois.empty() && dense) {
+      const int64_t boxSize[3] = {(int64_t)roiSize[0], (int64_t)roiSize[1], (int64_t)roiSize[2]};
+      int64_t numRows = 0;
+      engine.check(ife_bag_image_dense(engine.ctx(), image->GetBufferPointer(), IFE_F32, mask->GetBufferPointer(),
+                                       IFE_U16, roiMaskPath.empty() ? nullptr : roiMask->GetBufferPointer(), IFE_U16,
+                                       &d, scales.data(), (int)scales.size(), boxSize, edges.data(),
+                                       (int)(histSize - 1), counts.data(), (int64_t)rois.size(), &numRows,
+                                       IFE_MEM_HOST),
+                   toolName);
+      if (numRows != (int64_t)rois.size()) {  // .ROIInfo and .bag would disagree
+        std::ostringstream msg;
+        msg << "the device counted " << numRows << " dense regions, the generator " << rois.size();
+        throw itk::ExceptionObject(msg.str().c_str(), toolName);
+      }
+    } else if (!rois.empty() && intensity)  // the image itself is the one-component "feature volume"
       engine.check(ife_roi_histograms(engine.ctx(), image->GetBufferPointer(), IFE_INTERLEAVED, 1,
                                       mask->GetBufferPointer(), IFE_U16, &d, boxes.data(), (int)rois.size(),
                                       edges.data(), (int)(histSize - 1), counts.data(), IFE_MEM_HOST),

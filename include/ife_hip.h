@@ -105,7 +105,12 @@ typedef enum {
    * planes go from memory straight into an LDS ring several planes ahead of the arithmetic
    * (no staging registers, counted waits); 0: the register-staged form everywhere.  Same
    * arithmetic function, same results bit for bit. */
-  IFE_OPT_FEAT_RING = 10
+  IFE_OPT_FEAT_RING = 10,
+  /* Upper bound in MiB on the scratch of the dense bag calls (the planes of the box passes and,
+   * in ife_bag_image_dense, the features of a group of scales): 0 (default) sizes the groups
+   * from the free device memory.  Bins and scales then go through in smaller groups; results
+   * never change. */
+  IFE_OPT_DENSE_SCRATCH_MB = 11
 } ife_option;
 
 typedef struct {
@@ -408,6 +413,51 @@ int ife_bag_image(ife_ctx *ctx, const void *image, int image_dtype, const void *
                   int mask_dtype, const ife_volume_desc *vol, const float *sigmas, int n_sigmas,
                   const int64_t *rois, int n_rois, const float *edges, int n_edges,
                   uint32_t *counts, int mem);
+
+/* ---- the dense bag: one region per mask voxel (tools/MakeBagDense.cxx:239-250) ------------- *
+ * Conventions of the three calls: size = {sx, sy, sz} in voxels, each >= 1.  Voxel (x, y, z) is a
+ * centre when gen_mask != 0 there and the box [x - sx/2, x - sx/2 + sx) x [y - sy/2, ...) x
+ * [z - sz/2, ...) lies inside the volume; the division is integer division
+ * (include/ife/ROI/DenseROIGenerator.hxx:35-40), so even sizes are off-centre by design.  Regions
+ * are numbered in raster order of their centres, x fastest.  A box larger than the volume gives
+ * zero regions, which is not an error.  Masks are IFE_U8 or IFE_U16.  Volumes of up to 2^32-1
+ * voxels (regions are numbered in 32 bits; IFE_E_SIZE beyond); the number of regions is not
+ * limited to int.  The calls block in both memory modes (the region count comes to the host). */
+
+/* DenseROIGenerator<TMask>::generate(size): the boxes {x0,y0,z0,sx,sy,sz} of all centres.
+ * rois == NULL: only *n_rois is written.  Otherwise up to `capacity` boxes are written;
+ * IFE_E_SIZE (with *n_rois set, nothing written) when there are more.  gen_mask and rois follow
+ * `mem`, *n_rois is a HOST scalar. */
+int ife_dense_rois(ife_ctx *ctx, const void *gen_mask, int gen_mask_dtype,
+                   const ife_volume_desc *vol, const int64_t size[3],
+                   int64_t *n_rois, int64_t *rois, int64_t capacity, int mem);
+
+/* The rows ife_roi_histograms would give for those boxes, without the boxes:
+ * counts[(roi*ncomp + c)*(n_edges+1) + bin], voxels with mask != 0 only, DenseHistogram bins (a
+ * NaN value goes to bin 0, as there).  gen_mask NULL: mask decides the centres too.  Same capacity
+ * rule (capacity in rows; IFE_E_SIZE with *n_rois set and nothing written); *n_rois is a HOST
+ * scalar.  The counts are separable box sums of per-voxel bin codes (csrc/dense_kernels.hpp), so
+ * the work per region does not depend on the box.
+ * Limits: 1 <= n_edges <= 254 (IFE_E_ARG beyond): the bin of a voxel is kept in one byte and the
+ * value 255 stands for "not in the mask".  The running sums are one byte wide after the x pass,
+ * two after y and four after z: sx <= 255, sx*sy <= 65535 and sx*sy*sz <= 2^32-1 (IFE_E_SIZE
+ * beyond; 41^3 and 101^3 are inside).  IFE_E_NOMEM when the scratch of one bin of one component
+ * (4 bytes per voxel) does not fit. */
+int ife_dense_roi_histograms(ife_ctx *ctx, const float *features, int layout, int ncomp,
+                             const void *mask, int mask_dtype, const void *gen_mask,
+                             int gen_mask_dtype, const ife_volume_desc *vol, const int64_t size[3],
+                             const float *edges, int n_edges, uint32_t *counts,
+                             int64_t capacity, int64_t *n_rois, int mem);
+
+/* One image of MakeBagDense: ife_bag_image with the dense rule in place of the box list (labels
+ * clamped to {0,1}, a5 at every scale, the rows above per scale).  edges and counts are HOST
+ * arrays laid out as in ife_bag_image ([n_rois][n_sigmas*8][n_edges+1]); mem describes image,
+ * mask and gen_mask.  Limits as for ife_dense_roi_histograms. */
+int ife_bag_image_dense(ife_ctx *ctx, const void *image, int image_dtype, const void *mask,
+                        int mask_dtype, const void *gen_mask, int gen_mask_dtype,
+                        const ife_volume_desc *vol, const float *sigmas, int n_sigmas,
+                        const int64_t size[3], const float *edges, int n_edges,
+                        uint32_t *counts, int64_t capacity, int64_t *n_rois, int mem);
 
 /* The tool's `samples( scales.size() * numFeatures )` (:165-166): one growing column per
  * (scale, feature), kept in device memory.  Belongs to the context it was created on. */
