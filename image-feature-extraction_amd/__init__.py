@@ -59,6 +59,7 @@ EXPORTS = (
     "ife_samples_add_features", "ife_samples_add_image", "ife_samples_sort",
     "ife_samples_equalized_edges", "ife_samples_read_column",
     "ife_signed_distance_map", "ife_expected_distance",
+    "ife_stage_recursive_gaussian_order", "ife_normalized_convolution_jet", "ife_differential_features",
 )
 
 
@@ -179,6 +180,10 @@ def load_library():
     lib.ife_signed_distance_map.argtypes = [vp, vp, i32, vd, i32, i32, vp, i32]
     lib.ife_expected_distance.argtypes = [vp, vp, i32, vp, vd, C.POINTER(C.c_double),
                                           C.POINTER(i64), i32]
+    lib.ife_stage_recursive_gaussian_order.argtypes = [vp, vp, vp, vd, i32, C.c_double, i32]
+    lib.ife_normalized_convolution_jet.argtypes = [vp, f32p, f32p, vd, C.c_double, f32p, i32, i32]
+    lib.ife_differential_features.argtypes = [vp, vp, i32, vp, i32, vd, C.POINTER(C.c_float), i32,
+                                              f32p, i32, i32]
     _lib = lib
     return lib
 
@@ -363,6 +368,35 @@ class Context:
             len(sigmas), out.ctypes.data, layout, MEM_HOST))
         return out
 
+    def normalized_convolution_jet(self, image, certainty, sigma, spacing=(1.0, 1.0, 1.0),
+                                   layout=INTERLEAVED):
+        """U = {a*cT}/{a*c} with its gradient and Hessian by the quotient rule: (nz, ny, nx, 10) or
+        (10, nz, ny, nx), components U, g_x, g_y, g_z, h_xx, h_xy, h_xz, h_yy, h_yz, h_zz."""
+        image = np.ascontiguousarray(image, np.float32)
+        certainty = np.ascontiguousarray(certainty, np.float32)
+        d = _desc(image.shape, spacing)
+        out = np.empty(image.shape + (10,) if layout == INTERLEAVED else (10,) + image.shape,
+                       np.float32)
+        self._chk(self._lib.ife_normalized_convolution_jet(
+            self._h, image.ctypes.data, certainty.ctypes.data, C.byref(d), float(sigma),
+            out.ctypes.data, layout, MEM_HOST))
+        return out
+
+    def differential_features(self, image, mask, sigmas, spacing=(1.0, 1.0, 1.0),
+                              layout=INTERLEAVED):
+        """emphysema_features with gradient and Hessian from the differential normalized
+        convolution: shape (S, nz, ny, nx, 8) or (S, 8, nz, ny, nx)."""
+        image, idt = _image_arg(image)
+        mask, mdt, mptr = _mask_arg(mask)
+        d = _desc(image.shape, spacing)
+        sig = _sigma_arg(sigmas)
+        shp = image.shape + (8,) if layout == INTERLEAVED else (8,) + image.shape
+        out = np.empty((len(sigmas),) + shp, np.float32)
+        self._chk(self._lib.ife_differential_features(
+            self._h, image.ctypes.data, idt, mptr, mdt, C.byref(d), sig,
+            len(sigmas), out.ctypes.data, layout, MEM_HOST))
+        return out
+
     def emphysema_features_stream(self, image, mask, sigmas, spacing=(1.0, 1.0, 1.0),
                                   layout=INTERLEAVED):
         """Generator over the scales: begin once, yield one 8-component volume per sigma."""
@@ -460,6 +494,21 @@ class Context:
             self._h, C.c_void_p(image_ptr), image_dtype, C.c_void_p(mask_ptr or 0), mask_dtype,
             C.byref(d), sig, len(sigmas), C.c_void_p(out_ptr), layout, MEM_DEVICE))
 
+    def differential_features_device(self, image_ptr, image_dtype, mask_ptr, mask_dtype, shape_zyx,
+                                     spacing, sigmas, out_ptr, layout=INTERLEAVED):
+        d = _desc(shape_zyx, spacing)
+        sig = _sigma_arg(sigmas)
+        self._chk(self._lib.ife_differential_features(
+            self._h, C.c_void_p(image_ptr), image_dtype, C.c_void_p(mask_ptr or 0), mask_dtype,
+            C.byref(d), sig, len(sigmas), C.c_void_p(out_ptr), layout, MEM_DEVICE))
+
+    def normalized_convolution_jet_device(self, image_ptr, certainty_ptr, shape_zyx, spacing, sigma,
+                                          out_ptr, layout=INTERLEAVED):
+        d = _desc(shape_zyx, spacing)
+        self._chk(self._lib.ife_normalized_convolution_jet(
+            self._h, C.c_void_p(image_ptr), C.c_void_p(certainty_ptr), C.byref(d), float(sigma),
+            C.c_void_p(out_ptr), layout, MEM_DEVICE))
+
     def fd_hessian_features_device(self, image_ptr, image_dtype, mask_ptr, mask_dtype, shape_zyx,
                                    spacing, out_ptr, layout=INTERLEAVED):
         d = _desc(shape_zyx, spacing)
@@ -480,6 +529,14 @@ class Context:
         self._chk(self._lib.ife_stage_recursive_gaussian(
             self._h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), C.byref(d), int(axis_xyz),
             float(sigma)))
+
+    def stage_recursive_gaussian_order(self, in_ptr, out_ptr, shape_zyx, spacing, axis_xyz, sigma,
+                                       order):
+        """One axis pass of ITK's recursive Gaussian of order 0, 1 or 2 (pixel units)."""
+        d = _desc(shape_zyx, spacing)
+        self._chk(self._lib.ife_stage_recursive_gaussian_order(
+            self._h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), C.byref(d), int(axis_xyz),
+            float(sigma), int(order)))
 
     def stage_recursive_gaussian_batch(self, in_ptrs, out_ptrs, shape_zyx, spacing, axis_xyz,
                                        sigmas, in_y_chunks=1):

@@ -888,4 +888,172 @@ __global__ __launch_bounds__(256) void diffconv_kernel(const float *__restrict__
   }
 }
 
+// =====================================================================================
+// Differential normalized convolution, complete to second order (DESIGN.md section 4,
+// "Differential features"): the jet of U = N/D by the quotient rule from the twenty fields
+// N[t] = F[t](cT), D[t] = F[t](c), t = 000, x, y, z, xx, xy, xz, yy, yz, zz, and the eight
+// features built from it.  Per voxel, in double, every operation rounded on its own (this
+// translation unit is built with -ffp-contract=off), in exactly this order:
+//   d = D[0];  U = N[0] / d;  U_i = (N[i] - U * D[i]) / d;
+//   U_ij = (((N[ij] - U_i * D[j]) - U_j * D[i]) - U * D[ij]) / d;
+//   g_i = U_i * r_i;  h_ij = U_ij * (r_i * r_j)            (r = 1 / spacing)
+// The stored float D[0] == 0 gives FLT_MAX in all ten (the Div functor's rule); the features of
+// such a voxel are built from those ten values.
+//
+// Pointwise: 20 floats and the mask in, 8 or 10 floats out, no LDS.  A lane takes four
+// consecutive voxels with one 16-byte load per field (80 registers of input; a wider piece
+// would spill), works them off one after the other and stores whole voxels (interleaved: two
+// 16-byte stores per voxel of eight components, five 8-byte ones per voxel of ten) or one
+// 16-byte piece per component (planar).  The fields are read once and the outputs are not read
+// again inside the call: non-temporal both ways.
+// =====================================================================================
+enum JetMode { JET_JET10 = 0, JET_FEATURES8 = 1 };
+template <int MODE>
+struct JetNOut {
+  static constexpr int value = MODE == JET_JET10 ? 10 : 8;
+};
+struct JetFields {
+  const float *n[10];  // F[t](image * certainty)
+  const float *d[10];  // F[t](certainty)
+};
+struct JetGeom {
+  int64_t nvox;  // voxels; also the element stride between planar components
+  double r[3];   // 1 / spacing
+  double rr[6];  // r_i * r_j for xx, xy, xz, yy, yz, zz
+  int pvec;      // planar: every component plane starts on a 16-byte boundary
+};
+
+template <int MODE, int TRIG>
+__device__ __forceinline__ void jet_point(const float (&N)[10], const float (&D)[10], const JetGeom &g,
+                                          float (&o)[JetNOut<MODE>::value]) {
+  double U, G[3], H[6];
+  if (D[0] != 0.0f) {
+    const double d = (double)D[0];
+    U = (double)N[0] / d;
+    double U1[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      U1[i] = ((double)N[1 + i] - U * (double)D[1 + i]) / d;
+      G[i] = U1[i] * g.r[i];
+    }
+    int p = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = i; j < 3; ++j, ++p) {
+        double t = (double)N[4 + p] - U1[i] * (double)D[1 + j];
+        t = t - U1[j] * (double)D[1 + i];
+        t = t - U * (double)D[4 + p];
+        H[p] = (t / d) * g.rr[p];
+      }
+  } else {
+    U = (double)FLT_MAX;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) G[i] = (double)FLT_MAX;
+#pragma unroll
+    for (int p = 0; p < 6; ++p) H[p] = (double)FLT_MAX;
+  }
+  if constexpr (MODE == JET_JET10) {
+    o[0] = (float)U;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[1 + i] = (float)G[i];
+#pragma unroll
+    for (int p = 0; p < 6; ++p) o[4 + p] = (float)H[p];
+  } else {
+    o[0] = (float)U;
+    double a = G[0] * G[0] + G[1] * G[1];
+    a = a + G[2] * G[2];
+    o[1] = (float)sqrt(a);
+    const EigFeat ef = eig_features<TRIG>((float)H[0], (float)H[1], (float)H[2], (float)H[3], (float)H[4],
+                                          (float)H[5]);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[2 + k] = ef.f[k];
+  }
+}
+
+// Pieces [0, n4) of four consecutive voxels.  Needs 16-byte aligned fields, a mask aligned to
+// four of its elements and an interleaved output aligned as include/ife_hip.h asks (the host
+// sends everything else through jet_kernel_scalar).  A wave whose voxels are all outside the
+// mask skips the arithmetic (scalar branch).
+template <int MODE, int TRIG, bool PLANAR, typename TM>
+__global__ __launch_bounds__(256) void jet_kernel_vec4(JetFields f, const TM *__restrict__ mask,
+                                                       float *__restrict__ out, JetGeom g, int64_t n4) {
+  constexpr int NOUT = JetNOut<MODE>::value;
+  typedef TM TM4 __attribute__((ext_vector_type(4)));
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    f32x4 vn[10], vd[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      vn[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(f.n[k]) + i);
+      vd[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(f.d[k]) + i);
+    }
+    TM4 m = {(TM)1, (TM)1, (TM)1, (TM)1};
+    if (mask != nullptr) m = reinterpret_cast<const TM4 *>(mask)[i];
+    f32x4 po[PLANAR ? NOUT : 1];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const bool keep = m[v] != (TM)0;
+      float o[NOUT];
+#pragma unroll
+      for (int k = 0; k < NOUT; ++k) o[k] = 0.0f;
+      if (__builtin_amdgcn_ballot_w64(keep) != 0) {
+        float N[10], D[10];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) { N[k] = vn[k][v]; D[k] = vd[k][v]; }
+        jet_point<MODE, TRIG>(N, D, g, o);
+#pragma unroll
+        for (int k = 0; k < NOUT; ++k) o[k] = keep ? o[k] : 0.0f;
+      }
+      if constexpr (PLANAR) {
+#pragma unroll
+        for (int k = 0; k < NOUT; ++k) po[k][v] = o[k];
+      } else if constexpr (NOUT == 8) {
+        f32x4 *q = reinterpret_cast<f32x4 *>(out + (4 * i + v) * 8);
+        IFE_FT_STORE(q, (f32x4){o[0], o[1], o[2], o[3]});
+        IFE_FT_STORE(q + 1, (f32x4){o[4], o[5], o[6], o[7]});
+      } else {
+        f32x2 *q = reinterpret_cast<f32x2 *>(out + (4 * i + v) * NOUT);
+#pragma unroll
+        for (int k = 0; k < NOUT / 2; ++k) IFE_FT_STORE(q + k, (f32x2){o[2 * k], o[2 * k + 1]});
+      }
+    }
+    if constexpr (PLANAR) {
+      if (g.pvec) {
+#pragma unroll
+        for (int k = 0; k < NOUT; ++k)
+          IFE_FT_STORE(reinterpret_cast<f32x4 *>(out + (int64_t)k * g.nvox) + i, po[k]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < NOUT; ++k)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) out[(int64_t)k * g.nvox + 4 * i + v] = po[k][v];
+      }
+    }
+  }
+}
+
+// Voxels [i0, i1) one at a time: the tail behind the last whole piece, and everything where a
+// base address rules the 16-byte form out.
+template <int MODE, int TRIG, bool PLANAR, typename TM>
+__global__ __launch_bounds__(256) void jet_kernel_scalar(JetFields f, const TM *__restrict__ mask,
+                                                         float *__restrict__ out, JetGeom g, int64_t i0,
+                                                         int64_t i1) {
+  constexpr int NOUT = JetNOut<MODE>::value;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = i0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < i1; i += stride) {
+    float N[10], D[10], o[NOUT];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) { N[k] = f.n[k][i]; D[k] = f.d[k][i]; }
+    const bool keep = mask == nullptr || mask[i] != (TM)0;
+    jet_point<MODE, TRIG>(N, D, g, o);
+#pragma unroll
+    for (int k = 0; k < NOUT; ++k) {
+      const float v = keep ? o[k] : 0.0f;
+      if constexpr (PLANAR) out[(int64_t)k * g.nvox + i] = v;
+      else out[i * NOUT + k] = v;
+    }
+  }
+}
+
 }  // namespace ife

@@ -93,13 +93,14 @@ enum KernelKind {
   KK_DENSE_CODE,
   KK_DENSE_XY,
   KK_DENSE_Z,
+  KK_JET,
   KK_COUNT
 };
 static_assert(KK_COUNT <= IFE_MAX_KERNEL_KINDS, "ife_get_kernel_times callers size their arrays by IFE_MAX_KERNEL_KINDS");
 const char *kKindNames[KK_COUNT] = {"iir_z", "iir_x", "iir_y", "zslab_sweep", "zslab_combine", "features", "eig_batch",
                                     "divide", "mask_f64", "prep", "sort_hist", "sort_scan",
                                     "sort_scatter", "gather", "edges", "dense_histogram", "edt_x", "edt_y",
-                                    "edt_z", "edt_reduce", "dense_code", "dense_box_xy", "dense_box_z"};
+                                    "edt_z", "edt_reduce", "dense_code", "dense_box_xy", "dense_box_z", "jet_features"};
 
 struct DevBuf {
   void *p = nullptr;
@@ -143,6 +144,7 @@ struct ife_ctx {
   // dense bag: centre flags and numbers, the scratch of the box passes, clamped labels and features
   DevBuf dn_centres, dn_ws, dn_feat;
   int dense_scratch_mb = 0;  // IFE_OPT_DENSE_SCRATCH_MB: 0 = sized from the free device memory
+  DevBuf dj_ws;  // differential convolution: the field slots of one scale (diff_capi.inc)
   // streaming form of the scale loop (ife_emphysema_features_begin / _fetch / _end)
   DevBuf sc_out;                     // all scales, device resident
   std::vector<hipEvent_t> sc_done;   // one per scale: its feature launch has finished
@@ -1027,7 +1029,7 @@ void ife_ctx_destroy(ife_ctx *ctx) {
   std::vector<DevBuf *> bufs = {&ctx->pre[0], &ctx->pre[1], &ctx->st_img, &ctx->st_mask,
                                 &ctx->st_aux, &ctx->st_out, &ctx->sc_out, &ctx->edt_g,
                                 &ctx->edt_i, &ctx->edt_d2, &ctx->edt_part, &ctx->dn_centres,
-                                &ctx->dn_ws, &ctx->dn_feat};
+                                &ctx->dn_ws, &ctx->dn_feat, &ctx->dj_ws};
   for (auto &sl : ctx->fld)
     for (auto &b : sl) bufs.push_back(&b);
   for (auto &b : ctx->ck_y) bufs.push_back(&b);
@@ -1425,6 +1427,11 @@ int ife_stage_prepare(ife_ctx *ctx, const void *image, int image_dtype, const vo
 
 int ife_stage_recursive_gaussian(ife_ctx *ctx, const float *in, float *out,
                                  const ife_volume_desc *vol, int axis, double sigma) {
+  return ife_stage_recursive_gaussian_order(ctx, in, out, vol, axis, sigma, 0);
+}
+
+int ife_stage_recursive_gaussian_order(ife_ctx *ctx, const float *in, float *out,
+                                       const ife_volume_desc *vol, int axis, double sigma, int order) {
   int rc = bind(ctx);
   if (rc) return rc;
   if ((rc = check_vol(ctx, vol, false))) return rc;
@@ -1433,9 +1440,10 @@ int ife_stage_recursive_gaussian(ife_ctx *ctx, const float *in, float *out,
   if ((rc = check_axis(ctx, axis))) return rc;
   if ((rc = check_sigma(ctx, sigma))) return rc;
   if ((rc = check_axis_len(ctx, vol, axis))) return rc;
+  if (order < 0 || order > 2) return fail(ctx, IFE_E_ARG, "the order of the recursive Gaussian must be 0, 1 or 2");
   const float *ins[1] = {in};
   float *outs[1] = {out};
-  return launch_iir(ctx, vol, axis, 1, ins, outs, &sigma);
+  return launch_iir(ctx, vol, axis, 1, ins, outs, &sigma, 1, &order);
 }
 
 int ife_stage_recursive_gaussian_batch(ife_ctx *ctx, int njobs, const float *const *in,
@@ -1598,4 +1606,5 @@ int ife_reset_kernel_times(ife_ctx *ctx) {
 #include "stats_capi.inc"
 #include "distance_capi.inc"
 #include "dense_capi.inc"
+#include "diff_capi.inc"
 #include "multi_capi.inc"

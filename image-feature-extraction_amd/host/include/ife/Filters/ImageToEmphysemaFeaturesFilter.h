@@ -18,9 +18,19 @@
 // later ones.  Without the hint every scale is one self-contained call, as in the reference.
 // The same holds with IFE_DEVICES (several devices, Z-slabs): one upload of the slabs and one
 // prepass for all announced scales (ife_multi_emphysema_features_begin), a fetch per scale.
+//
+// A second addition: SetUseDifferentialConvolution(true) takes gradient magnitude and Hessian
+// from the differential normalized convolution (ife_differential_features: the applicability is
+// differentiated, not the result, so nothing is read where the normalized convolution is an
+// extrapolation) instead of finite differences of the smoothed value.  The environment variable
+// IFE_DIFFERENTIAL sets the initial value (unset or 0: off), because the tools keep the
+// reference's flags.  Every Update() is then one self-contained call for the current sigma (no
+// begin/fetch streaming); with several devices (IFE_DEVICES) it throws.
 #ifndef __ImageToEmphysemaFeaturesFilter_h
 #define __ImageToEmphysemaFeaturesFilter_h
 
+#include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "ife/Host/Engine.h"
@@ -48,6 +58,12 @@ class ImageToEmphysemaFeaturesFilter {
     dirty_ = true;
   }
   ScalarRealType GetSigma() const { return sigma_; }
+  void SetUseDifferentialConvolution(bool on) {
+    if (on != differential_) { EndStream(); differential_ = on; dirty_ = true; }
+  }
+  bool GetUseDifferentialConvolution() const { return differential_; }
+  void UseDifferentialConvolutionOn() { SetUseDifferentialConvolution(true); }
+  void UseDifferentialConvolutionOff() { SetUseDifferentialConvolution(false); }
   static const size_t numFeatures = 8;  // .h:62
 
   void Modified() { dirty_ = true; }
@@ -65,6 +81,20 @@ class ImageToEmphysemaFeaturesFilter {
     int which = -1;
     for (size_t k = 0; k < scales_.size(); ++k)
       if (scales_[k] == (float)sigma_) { which = (int)k; break; }
+    if (differential_) {
+      if (e.multi())
+        throw ExceptionObject("the differential convolution runs on one device; unset IFE_DEVICES",
+                              "ImageToEmphysemaFeaturesFilter");
+      const float sig = (float)sigma_;
+      e.check(ife_differential_features(
+                  e.ctx(), image_->GetBufferPointer(), ife::host::ImageDType<PixelType>::value,
+                  mask_->GetBufferPointer(),
+                  ife::host::MaskDType<typename InputMaskType::PixelType>::value, &d, &sig, 1,
+                  out_->GetBufferPointer(), IFE_INTERLEAVED, IFE_MEM_HOST),
+              "ImageToEmphysemaFeaturesFilter");
+      dirty_ = false;
+      return;
+    }
     if (ife_multi *multi = e.multi()) {  // IFE_DEVICES: Z-slabs over several devices
       const int idt = ife::host::ImageDType<PixelType>::value;
       const int mdt = ife::host::MaskDType<typename InputMaskType::PixelType>::value;
@@ -132,6 +162,11 @@ class ImageToEmphysemaFeaturesFilter {
   const InputMaskType *mask_ = nullptr;
   ScalarRealType sigma_ = 1.0;  // .hxx:18
   bool dirty_ = true;
+  bool differential_ = DifferentialFromEnvironment();
+  static bool DifferentialFromEnvironment() {
+    const char *v = std::getenv("IFE_DIFFERENTIAL");
+    return v && v[0] && std::strcmp(v, "0") != 0;
+  }
   typename OutputImageType::Pointer out_;
 };
 

@@ -53,7 +53,7 @@ typedef enum { IFE_F32 = 0, IFE_I16 = 1, IFE_U8 = 2, IFE_U16 = 3 } ife_dtype;
 typedef enum { IFE_INTERLEAVED = 0, IFE_PLANAR = 1 } ife_layout;
 typedef enum { IFE_MEM_HOST = 0, IFE_MEM_DEVICE = 1 } ife_mem;
 /* IFE_MEM_DEVICE pointers must be aligned to their element size, interleaved 8-component
- * outputs to 16 bytes and 6-component ones to 8 (vector stores); anything else is refused
+ * outputs to 16 bytes, 6- and 10-component ones to 8 (vector stores); anything else is refused
  * with IFE_E_ARG.  hipMalloc'ed buffers and whole voxels / planes inside them qualify. */
 
 /* Options for ife_ctx_set_option */
@@ -195,6 +195,29 @@ int ife_differential_normalized_convolution(ife_ctx *ctx, const float *image,
                                             const float *certainty, const ife_volume_desc *vol,
                                             double sigma, int axis, float *out, int mem);
 
+/* The complete form of that sketch: U = {a*cT}/{a*c} with its gradient and Hessian by the quotient
+ * rule, differentiating the applicability and never the result (no value of U outside the
+ * certainty's support enters a derivative).  cT = image * certainty (float).  For f in {cT, c} and
+ * every order triple (ox, oy, oz) with ox + oy + oz <= 2:
+ *   F[ox,oy,oz](f) = RG_y^oy(RG_x^ox(RG_z^oz(f)))
+ * RG_axis^order = ITK's recursive Gaussian of that order along that axis (pixel units), passes in
+ * the order z, x, y, a float image between passes, sigma in physical units.  N = F(cT), D = F(c),
+ * r_i = 1.0 / spacing_i.  Per voxel in double, every operation rounded on its own, in this order:
+ *   d    = D[000]
+ *   U    = N[000] / d
+ *   U_i  = (N[e_i] - U * D[e_i]) / d                                            i = x, y, z
+ *   U_ij = (((N[e_i+e_j] - U_i * D[e_j]) - U_j * D[e_i]) - U * D[e_i+e_j]) / d   i <= j
+ *   g_i  = U_i * r_i
+ *   h_ij = U_ij * (r_i * r_j)
+ * out10: the ten components (float)U, g_x, g_y, g_z, h_xx, h_xy, h_xz, h_yy, h_yz, h_zz in
+ * `layout`; all ten are FLT_MAX where the stored float D[000] == 0 (the Div functor's rule, as in
+ * the two calls above).  Every axis must be >= 4 voxels.  IFE_MEM_DEVICE: the interleaved output
+ * must be aligned to 8 bytes.  Workspace: 140 bytes per voxel (csrc/diff_capi.inc); IFE_E_NOMEM
+ * when it does not fit. */
+int ife_normalized_convolution_jet(ife_ctx *ctx, const float *image, const float *certainty,
+                                   const ife_volume_desc *vol, double sigma, float *out10, int layout,
+                                   int mem);
+
 /* ---- a5 + a9: ImageToEmphysemaFeaturesFilter, one execution per scale ------------ */
 
 /* SetInputImage + SetInputMask + for each sigma {SetSigma; Update; GetOutput}
@@ -208,6 +231,18 @@ int ife_differential_normalized_convolution(ife_ctx *ctx, const float *image,
 int ife_emphysema_features(ife_ctx *ctx, const void *image, int image_dtype, const void *mask,
                            int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
                            int n_sigmas, float *out, int layout, int mem);
+
+/* The same eight features (order of IFE_FEATURE_NAMES) from the jet of
+ * ife_normalized_convolution_jet instead of finite differences of the smoothed value, which next
+ * to the mask border read the normalized convolution where it is an extrapolation.  No
+ * counterpart in the reference.  Per voxel: S = (float)U; G = (float)sqrt((g_x*g_x + g_y*g_y) +
+ * g_z*g_z) in double; the six float h through EigenvalueFeaturesFunctor<float> in the context's
+ * trig mode; every component mask != 0 ? v : 0.  Arguments, certainty (the mask value, NULL = all
+ * ones), output order and alignment as in ife_emphysema_features.  A voxel with mask != 0 and
+ * D[000] == 0 gets the features of a jet of ten FLT_MAX.  Scales run one after the other. */
+int ife_differential_features(ife_ctx *ctx, const void *image, int image_dtype, const void *mask,
+                              int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
+                              int n_sigmas, float *out, int layout, int mem);
 
 /* The scale loop of tools/ExtractFeatures.cxx:132-154 as a stream: _begin uploads image and
  * mask ONCE (host pointers), runs Cast + Multiply once and enqueues every scale, leaving the
@@ -266,6 +301,11 @@ int ife_stage_prepare(ife_ctx *ctx, const void *image, int image_dtype, const vo
  * caller keeps ITK's order z, x, y.  Not in place. */
 int ife_stage_recursive_gaussian(ife_ctx *ctx, const float *in, float *out,
                                  const ife_volume_desc *vol, int axis, double sigma);
+/* One axis pass of itk::RecursiveGaussianImageFilter of order 0 (ZeroOrder, the call above), 1
+ * (FirstOrder) or 2 (SecondOrder), NormalizeAcrossScale off: the derivative filters answer in
+ * pixel units along `axis`.  IFE_E_ARG for any other order.  Not in place. */
+int ife_stage_recursive_gaussian_order(ife_ctx *ctx, const float *in, float *out,
+                                       const ife_volume_desc *vol, int axis, double sigma, int order);
 /* The same over njobs (<= 8) float volumes of one geometry in a single launch, each with
  * its own sigma: numerator and denominator of several scales.  A slab host needs this to
  * keep the device full (a 64-plane slab has too few lines for one job per launch).
