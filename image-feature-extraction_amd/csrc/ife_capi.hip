@@ -136,7 +136,7 @@ struct ife_ctx {
   // through the line kernels together)
   DevBuf fld[IFE_MAX_SLOTS][4];
   DevBuf pre[2];  // image*certainty and certainty as float (prepass, shared by all scales)
-  DevBuf ck_y[IIR_MAX_JOBS], ck_x[IIR_MAX_JOBS];  // one checkpoint area per concurrent job
+  DevBuf ck_y[IIR_MAX_JOBS];  // one checkpoint area per concurrent job
   DevBuf st_img, st_mask, st_aux, st_out;  // HOST-mode staging
   // distance map: candidate stacks of the line passes (values, indices), the squared map and
   // the per-line partial sums of the expected distance
@@ -454,16 +454,14 @@ size_t ck_pairs(int64_t n, int K) { return (size_t)((n + K - 1) / K); }
 
 int ensure_ck(ife_ctx *ctx, const ife_volume_desc *v, int njobs) {
   const int K = 8;  // sized for the smallest register block any axis may run with
-  size_t need_y = 0, need_x = 0;
+  size_t need_y = 0;
   for (int a = 0; a < 3; ++a) {
     IirGeom g = geom_for_axis(v, a);
     const size_t np = ck_pairs(g.n, K);
     need_y = std::max(need_y, np * 4 * (size_t)g.nlines * sizeof(double));
-    need_x = std::max(need_x, np * 3 * (size_t)g.nlines * sizeof(float));
   }
   for (int j = 0; j < njobs; ++j) {
     int rc = ensure(ctx, ctx->ck_y[j], need_y);
-    if (!rc) rc = ensure(ctx, ctx->ck_x[j], need_x);
     if (rc) return rc;
   }
   return IFE_OK;
@@ -515,7 +513,6 @@ int launch_iir(ife_ctx *ctx, const ife_volume_desc *v, int axis, int njobs,
     jobs.j[j].in = in[j];
     jobs.j[j].out = out[j];
     jobs.j[j].ck_y = (double *)ctx->ck_y[j].p;
-    jobs.j[j].ck_x = (float *)ctx->ck_x[j].p;
     if (in2) {
       if (!in2[j] || in2[j] == out[j] || reinterpret_cast<uintptr_t>(in2[j]) % 4)
         return fail(ctx, IFE_E_ARG, "bad denominator buffer");
@@ -1033,7 +1030,6 @@ void ife_ctx_destroy(ife_ctx *ctx) {
   for (auto &sl : ctx->fld)
     for (auto &b : sl) bufs.push_back(&b);
   for (auto &b : ctx->ck_y) bufs.push_back(&b);
-  for (auto &b : ctx->ck_x) bufs.push_back(&b);
   for (DevBuf *b : bufs)
     if (b->p) (void)hipFree(b->p);
   for (auto &r : ctx->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }

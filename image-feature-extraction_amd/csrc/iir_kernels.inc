@@ -8,12 +8,15 @@
 //
 // Mapping to the machine: one line per lane, 64 adjacent lines per wave.  A line is
 // walked in register blocks of K samples.
-//   forward sweep : causal recursion; at every block start the state
-//                   (y[i-1..i-4] as double, x[i-1..i-3] as float) is written to a
-//                   checkpoint array (44 B per line per K samples).
-//   backward sweep: per block, reload the checkpoint, recompute the K causal values
-//                   into registers, run the anticausal recursion over the same K
-//                   samples, and store float(causal + anticausal).
+//   forward sweep : causal recursion; three samples into every pair of blocks the four
+//                   newest causal values (double) are written to a checkpoint array
+//                   (32 B per line per 2K samples).
+//   backward sweep: per pair, reload the checkpoint -- it IS the causal value of the
+//                   pair's first three samples, and the x history behind it is those
+//                   samples --, recompute the other 2K-3 causal values, run the
+//                   anticausal recursion over the same 2K samples, and store
+//                   float(causal + anticausal).  The line's last pair, where the sweep
+//                   turns, takes its state from the forward sweep in registers.
 // This keeps the exact sequential double arithmetic of the reference (every
 // multiply and add rounds separately: the TU is built with -ffp-contract=off) while
 // the only extra HBM traffic is the checkpoint array.  The causal partial sums never
@@ -39,6 +42,8 @@
 #include <stdint.h>
 
 #include <stddef.h>
+
+#include <type_traits>
 
 #include "iir_types.hpp"
 
@@ -317,12 +322,14 @@ struct SrcF32 {
 
 struct Checkpoint {
   double *y;
-  float *x;
 };
 
-// The recursion state is saved once per PAIR of register blocks (every 2K samples); the
-// three input samples in front of the pair are re-read from the input (they sit in rows
-// the sweep loads anyway).  That is 32 B per line per 32 samples each way.
+// The recursion state is saved once per PAIR of register blocks (every 2K samples), behind
+// the pair's third sample i0+2: y1..y4 = y[i0+2], y[i0+1], y[i0], y[i0-1].  The x history
+// that belongs to it is x[i0+2..i0], samples of the pair itself, so nothing in front of the
+// pair is read again, and the first three causal values of the pair are not recomputed: they
+// are y3, y2, y1, the very doubles the recomputation would produce.  That is 32 B per line
+// per 2K samples each way, for the strided and the contiguous kernel alike.
 __device__ __forceinline__ void ck_store(const Checkpoint &ck, int64_t pair, int64_t nl,
                                          int64_t Lw, uint32_t lane, const CausalState &s) {
   const rsrc_t ry = IFE_CK_RSRC(ck.y + (pair * 4) * nl + Lw);
@@ -340,25 +347,6 @@ __device__ __forceinline__ void ck_load(const Checkpoint &ck, int64_t pair, int6
   s.y2 = ck_ld_f64(ry, lane * 8u, sy);
   s.y3 = ck_ld_f64(ry, lane * 8u, 2u * sy);
   s.y4 = ck_ld_f64(ry, lane * 8u, 3u * sy);
-}
-
-// The contiguous-axis kernel cannot re-read the x history cheaply (it would be 64
-// scattered 4-B loads per wave), so it keeps it beside the state: 12 B per line per pair.
-__device__ __forceinline__ void ck_store_x(const Checkpoint &ck, int64_t pair, int64_t nl,
-                                           int64_t Lw, uint32_t lane, const CausalState &s) {
-  const rsrc_t rx = make_rsrc(ck.x + (pair * 3) * nl + Lw);
-  const uint32_t sx = (uint32_t)nl * 4u;
-  ck_st_f32(rx, lane * 4u, 0u, (float)s.x1);
-  ck_st_f32(rx, lane * 4u, sx, (float)s.x2);
-  ck_st_f32(rx, lane * 4u, 2u * sx, (float)s.x3);
-}
-__device__ __forceinline__ void ck_load_x(const Checkpoint &ck, int64_t pair, int64_t nl,
-                                          int64_t Lw, uint32_t lane, CausalState &s) {
-  const rsrc_t rx = make_rsrc(ck.x + (pair * 3) * nl + Lw);
-  const uint32_t sx = (uint32_t)nl * 4u;
-  s.x1 = (double)ck_ld_f32(rx, lane * 4u, 0u);
-  s.x2 = (double)ck_ld_f32(rx, lane * 4u, sx);
-  s.x3 = (double)ck_ld_f32(rx, lane * 4u, 2u * sx);
 }
 
 // The first block of a pair is run twice from the same state (once to reach the second
@@ -501,7 +489,7 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
   const SrcF32 src{is_den ? J.in2 : J.in};
   float *__restrict__ out = J.out;
   const IirCoefMain c = main_coefs(J.c);  // interior recursion; border blocks read edge_coefs(blk.job)
-  const Checkpoint ck{is_den ? J.ck_y2 : J.ck_y, J.ck_x};
+  const Checkpoint ck{is_den ? J.ck_y2 : J.ck_y};
   int64_t Lw = PAIRED ? uniform64((int64_t)blk.group * 128 + (int64_t)(wave_id & 1u) * 64)
                       : uniform64((int64_t)blk.group * blockDim.x + (int64_t)(threadIdx.x & ~63u));
   const bool wave_dead = Lw >= g.nlines;
@@ -526,7 +514,7 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
 #error "the strided kernel parks the causal values of a pair in LDS"
 #endif
 
-  // ---------------- forward sweep: a checkpoint in front of every pair >= 1 ----------------
+  // ---------------- forward sweep: a checkpoint for every pair 1 .. np-2 ----------------
   // Pairs 0 .. np-2 (all complete; the last pair is only read by the backward sweep), two
   // pairs of samples in flight in two register sets.
   // Constant lines: every sample of the line equals its first one (tracked here for one
@@ -534,6 +522,11 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
   // the backward sweep, once the last pair has been seen.
   bool fwd_const = true;
   float fwd_ref = 0.0f;
+  // The state in front of the LAST pair never goes through memory: the forward sweep ends
+  // there and the backward sweep starts there, so it is handed over in registers.
+  CausalState turn;
+  turn.x1 = turn.x2 = turn.x3 = 0.0;
+  turn.y1 = turn.y2 = turn.y3 = turn.y4 = 0.0;
   {
     float a0[K], a1[K], b0[K], b1[K];
     CausalState s;
@@ -553,9 +546,13 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
         }
       }
     };
-    auto run_pair = [&](const float (&u)[K], const float (&v)[K]) {
+    // pair p, 1 <= p <= np-2: its checkpoint is taken THREE samples into the pair (ck_store)
+    auto run_pair = [&](int p, const float (&u)[K], const float (&v)[K]) {
 #pragma unroll
-      for (int j = 0; j < K; ++j) causal_step(s, (double)u[j], c);
+      for (int j = 0; j < 3; ++j) causal_step(s, (double)u[j], c);
+      ck_store(ck, p, nl, Lw, cl, s);
+#pragma unroll
+      for (int j = 3; j < K; ++j) causal_step(s, (double)u[j], c);
       track(u);
 #pragma unroll
       for (int j = 0; j < K; ++j) causal_step(s, (double)v[j], c);
@@ -578,22 +575,17 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
 #pragma unroll
         for (int j = 0; j < K; ++j) causal_step(s, (double)a1[j], c);
         track(a1);
-        ck_store(ck, 1, nl, Lw, cl, s);
       }
       load_pair_f(2, a0, a1);
       int p = 1;  // b holds pair p, a holds pair p+1
       for (; p + 1 < nfp; p += 2) {
-        run_pair(b0, b1);
-        ck_store(ck, p + 1, nl, Lw, cl, s);
+        run_pair(p, b0, b1);
         load_pair_f(p + 2, b0, b1);
-        run_pair(a0, a1);
-        ck_store(ck, p + 2, nl, Lw, cl, s);
+        run_pair(p + 1, a0, a1);
         load_pair_f(p + 3, a0, a1);
       }
-      if (p < nfp) {
-        run_pair(b0, b1);
-        ck_store(ck, p + 1, nl, Lw, cl, s);
-      }
+      if (p < nfp) run_pair(p, b0, b1);
+      turn = s;
     }
   }
 
@@ -601,8 +593,6 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
   {
     float xa[K], xb[K];  // blocks 2p and 2p+1 of the current pair
     float na[K], nb2[K];  // the next pair (p-1), in flight
-    float h1 = 0.f, h2 = 0.f, h3 = 0.f;     // x[i-1..i-3] in front of the current pair
-    float nh1 = 0.f, nh2 = 0.f, nh3 = 0.f;  // the same for the next pair
     AntiState a;
     auto load_pair = [&](int p, float (&pa)[K], float (&pb)[K], bool clampn) {
       const int64_t i0 = (int64_t)(2 * p * K);
@@ -621,12 +611,6 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
         for (int j = 0; j < K; ++j)
           pb[j] = src.ld_last(B, voff, ((uint32_t)(K + j) < lastj ? (uint32_t)(K + j) : lastj) * sst);
       }
-    };
-    auto load_hist = [&](int p, float &q1, float &q2, float &q3) {
-      const auto B = src.at(wbase + (int64_t)(2 * p * K - 3) * st);  // p >= 1
-      q3 = src.ld(B, voff, 0u);
-      q2 = src.ld(B, voff, sst);
-      q1 = src.ld(B, voff, 2u * sst);
     };
     // checkpoint of the current pair and, in flight, of the next one
     CausalState sc, sn;
@@ -654,10 +638,6 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
           if (i0 + j < n) buf_st_out_f32(ro, voff * 4u, (uint32_t)j * sst * 4u, cval);
       }
       return;
-    }
-    if (np > 1) {
-      load_hist(np - 1, h1, h2, h3);
-      ck_load(ck, np - 1, nl, Lw, cl, sc);
     }
     {
       // x[n-1]: the clamped loads make every slot past the line end hold it
@@ -690,7 +670,6 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
     auto rotate = [&]() {
 #pragma unroll
       for (int j = 0; j < K; ++j) { xa[j] = na[j]; xb[j] = nb2[j]; }
-      h1 = nh1; h2 = nh2; h3 = nh3;
       sc.y1 = sn.y1; sc.y2 = sn.y2; sc.y3 = sn.y3; sc.y4 = sn.y4;
     };
 
@@ -698,14 +677,17 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
     // (2p+2)K + 4 <= n): no border form, no ragged block, every memory operation unconditional ----
     auto steady_iter = [&](int p) {
       const int64_t i0 = (int64_t)(2 * p * K);
+      // the checkpoint IS the causal value of the pair's first three samples (and y[i0-1]),
+      // and the x history behind it is the samples themselves
       CausalState s;
       s.y1 = sc.y1; s.y2 = sc.y2; s.y3 = sc.y3; s.y4 = sc.y4;
-      s.x1 = (double)h1; s.x2 = (double)h2; s.x3 = (double)h3;
+      s.x1 = (double)xa[2]; s.x2 = (double)xa[1]; s.x3 = (double)xa[0];
+      col[0] = sc.y3; col[64] = sc.y2; col[128] = sc.y1;
       // (scheduling fences: left alone, the scheduler converts and loads far ahead across this
       // branch-free stretch and the allocation no longer fits four / three waves per SIMD)
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int j = 0; j < K; ++j) {
+      for (int j = 3; j < K; ++j) {
         col[j * 64] = causal_step(s, (double)xa[j], c);
         if (j % IFE_IIR_FENCE == IFE_IIR_FENCE - 1) __builtin_amdgcn_sched_barrier(0);
       }
@@ -719,7 +701,6 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
       // the next pair is requested here, not at the top: it is only needed an iteration later,
       // and the causal half above is where the register demand peaks
       load_pair(p - 1, na, nb2, false);
-      load_hist(p - 1, nh1, nh2, nh3);
       ck_load(ck, p - 1, nl, Lw, cl, sn);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -754,31 +735,38 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
     };
 
     // ---- any pair: border forms at the line's ends, ragged last blocks, no predecessor ----
-    auto general_iter = [&](int p) {
+    // TURN (a compile-time tag): the line's last pair, whose state comes from the forward
+    // sweep in registers; its own instance, so that `turn` is dead before the steady loop.
+    auto general_iter = [&](int p, auto turn_tag) {
+      constexpr bool TURN = decltype(turn_tag)::value;
       const int64_t i0 = (int64_t)(2 * p * K), i1 = i0 + K;
       const IirCoef ce = edge_coefs(blk.job);
       if (p > 0) {
         load_pair(p - 1, na, nb2, false);
-        if (p > 1) {
-          load_hist(p - 1, nh1, nh2, nh3);
-          ck_load(ck, p - 1, nl, Lw, cl, sn);
-        }
-      }
-      CausalState s0;
-      if (p > 0) {
-        s0.y1 = sc.y1; s0.y2 = sc.y2; s0.y3 = sc.y3; s0.y4 = sc.y4;
-        s0.x1 = (double)h1; s0.x2 = (double)h2; s0.x3 = (double)h3;
-      } else {
-        const double x0 = (double)xa[0];
-        s0.x1 = s0.x2 = s0.x3 = x0;
-        s0.y1 = s0.y2 = s0.y3 = s0.y4 = x0;
+        if (p > 1) ck_load(ck, p - 1, nl, Lw, cl, sn);
       }
       const bool head = p == 0;                 // border form at the line start
       const bool tail = i1 + K + 4 > n;         // second block touches the last 4 samples
       const rsrc_t ro = PAIRED ? IFE_OUT_RSRC_RANGE(out + wbase + i0 * st, out_range) : IFE_OUT_RSRC(out + wbase + i0 * st);
       const bool edge = head || (i0 + K + 4 > n);
-      CausalState s = s0;
-      causal_run_park<K>(s, xa, col, ce, i0, n, edge);
+      CausalState s;
+      if (head || TURN) {
+        if (head) {
+          const double x0 = (double)xa[0];
+          s.x1 = s.x2 = s.x3 = x0;
+          s.y1 = s.y2 = s.y3 = s.y4 = x0;
+        } else {
+          s = turn;
+        }
+        causal_run_park<K>(s, xa, col, ce, i0, n, edge);
+      } else {
+        // a complete pair behind the line start: from its checkpoint, as in the steady iteration
+        s.y1 = sc.y1; s.y2 = sc.y2; s.y3 = sc.y3; s.y4 = sc.y4;
+        s.x1 = (double)xa[2]; s.x2 = (double)xa[1]; s.x3 = (double)xa[0];
+        col[0] = sc.y3; col[64] = sc.y2; col[128] = sc.y1;
+#pragma unroll
+        for (int j = 3; j < K; ++j) col[j * 64] = causal_step(s, (double)xa[j], ce);
+      }
       if (i1 < n) {  // second block of the pair
         causal_run_park<K>(s, xb, col + K * 64, ce, i1, n, tail);
         anti_run_parked<K>(a, xb, col + K * 64, ce, i1, n, tail);
@@ -805,7 +793,8 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
     };
 
     const int p_hi = (int)((n - 4) / (2 * K)) - 1;  // largest p with (2p+2)K + 4 <= n
-    int p = np - 1;
+    general_iter(np - 1, std::true_type{});
+    int p = np - 2;
     while (p >= 0) {
       if (p >= 2 && p <= p_hi) {
         // The compiler's wait counts inside the loop are only as good as what it knows at the
@@ -818,7 +807,7 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
           --p;
         } while (p >= 2);
       } else {
-        general_iter(p);
+        general_iter(p, std::false_type{});
         --p;
       }
     }
@@ -840,7 +829,7 @@ __global__ __launch_bounds__(256) void iir_strided1_kernel(IirJobs jobs, IirGeom
   const SrcF32 src{J.in};
   float *__restrict__ out = J.out;
   const IirCoef c = J.c;
-  const Checkpoint ck{J.ck_y, J.ck_x};
+  const Checkpoint ck{J.ck_y};
   const uint32_t lane = threadIdx.x & 63u;
   const int64_t Lw =
       uniform64((int64_t)blk.group * blockDim.x + (int64_t)(threadIdx.x & ~63u));
@@ -1070,7 +1059,7 @@ __global__ __launch_bounds__(256, 2) void iir_contig_kernel(IirJobs jobs, IirGeo
   const float *__restrict__ in = J.in;
   float *__restrict__ out = J.out;
   const IirCoefMain c = main_coefs(J.c);  // interior recursion; border tiles read edge_coefs(blk.job)
-  const Checkpoint ck{J.ck_y, J.ck_x};
+  const Checkpoint ck{J.ck_y};
   constexpr int W = 2 * K;  // tile width: two register blocks
   constexpr int P = XTile<W>::PITCH;
   constexpr int V = W / 4;     // 16-byte pieces per line and tile
@@ -1138,9 +1127,15 @@ __global__ __launch_bounds__(256, 2) void iir_contig_kernel(IirJobs jobs, IirGeo
 
   float xb[K];
 
-  // ---------------- forward sweep: a checkpoint in front of every tile >= 1 ----------------
+  // ---------------- forward sweep: a checkpoint for every tile 1 .. nt-2 ----------------
+  // As in the strided kernel the checkpoint of a tile is taken three samples into it (its x
+  // history is then the tile's own first three samples, and nothing but the four y values is
+  // kept), and the state in front of the last tile goes to the backward sweep in registers.
   bool fwd_const = true;  // constant lines, as in the strided kernel
   float fwd_ref = 0.0f;
+  CausalState turn;
+  turn.x1 = turn.x2 = turn.x3 = 0.0;
+  turn.y1 = turn.y2 = turn.y3 = turn.y4 = 0.0;
   {
     CausalState s;
     // both blocks of tile t from LDS through the causal recursion (tile 0: border form)
@@ -1150,7 +1145,10 @@ __global__ __launch_bounds__(256, 2) void iir_contig_kernel(IirJobs jobs, IirGeo
         xtile_get<W, K>(tile, lane, h, xb);
         if (t > 0 || h > 0) {
 #pragma unroll
-          for (int j = 0; j < K; ++j) causal_step(s, (double)xb[j], c);
+          for (int j = 0; j < 3; ++j) causal_step(s, (double)xb[j], c);
+          if (t > 0 && h == 0 && live) ck_store(ck, t, nl, line0, lane, s);
+#pragma unroll
+          for (int j = 3; j < K; ++j) causal_step(s, (double)xb[j], c);
         } else {
           const IirCoef ce = edge_coefs(blk.job);
           const double x0 = (double)xb[0];
@@ -1173,8 +1171,6 @@ __global__ __launch_bounds__(256, 2) void iir_contig_kernel(IirJobs jobs, IirGeo
         commit_fill();
         issue_fill(1, mask_lt(1, ntf));
         fwd_tile(0);
-        ck_store(ck, 1, nl, line0, lane, s);
-        ck_store_x(ck, 1, nl, line0, lane, s);
         wave_lds_sync();
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see the strided kernel's steady loop
         for (int t = 1; t < ntf; ++t) {
@@ -1184,14 +1180,15 @@ __global__ __launch_bounds__(256, 2) void iir_contig_kernel(IirJobs jobs, IirGeo
           for (int h = 0; h < 2; ++h) {
             xtile_get<W, K>(tile, lane, h, xb);
 #pragma unroll
-            for (int j = 0; j < K; ++j) causal_step(s, (double)xb[j], c);
+            for (int j = 0; j < 3; ++j) causal_step(s, (double)xb[j], c);
+            if (h == 0) ck_store(ck, t, nl, line0, lane, s);
+#pragma unroll
+            for (int j = 3; j < K; ++j) causal_step(s, (double)xb[j], c);
             if (J.const_lines) {
 #pragma unroll
               for (int j = 0; j < K; ++j) fwd_const = fwd_const && same_bits(xb[j], fwd_ref);
             }
           }
-          ck_store(ck, t + 1, nl, line0, lane, s);
-          ck_store_x(ck, t + 1, nl, line0, lane, s);
           wave_lds_sync();  // reads of this tile are done before the next commit overwrites it
         }
       }
@@ -1199,13 +1196,10 @@ __global__ __launch_bounds__(256, 2) void iir_contig_kernel(IirJobs jobs, IirGeo
       for (int t = 0; t < ntf; ++t) {
         xtile_fill<W>(rows_in, tile, lane, nrows, pitch, (int64_t)t * W, n, vec_ok);
         fwd_tile(t);
-        if (live) {
-          ck_store(ck, t + 1, nl, line0, lane, s);
-          ck_store_x(ck, t + 1, nl, line0, lane, s);
-        }
         wave_lds_sync();  // reads of this tile are done before the next fill overwrites it
       }
     }
+    if (ntf > 0) turn = s;
   }
 
   // ---------------- backward sweep, one tile (pair of blocks) per iteration ----------------
@@ -1213,11 +1207,13 @@ __global__ __launch_bounds__(256, 2) void iir_contig_kernel(IirJobs jobs, IirGeo
     AntiState a;
     bool done = false;  // the constant-line shortcut has answered the whole line
     // plain form of one tile: fill, wait, compute with every border rule, drain
-    auto plain_tile = [&](int t) {
+    // TURN (a compile-time tag): the line's last tile, which starts from `turn`
+    auto plain_tile = [&](int t, auto turn_tag) {
+      constexpr bool TURN = decltype(turn_tag)::value;
       const int64_t i0 = (int64_t)t * W, i1 = i0 + K;
       const IirCoef ce = edge_coefs(blk.job);
       xtile_fill<W, IFE_IN2_AUX>(rows_in, tile, lane, nrows, pitch, i0, n, vec_ok);
-      if (t == nt - 1) {
+      if constexpr (TURN) {
         // x[n-1]: the clamped fill makes every slot past the line end hold it
         const double xN = (double)tile[lane * P + W - 1];
         a.x1 = a.x2 = a.x3 = a.x4 = xN;
@@ -1254,21 +1250,29 @@ __global__ __launch_bounds__(256, 2) void iir_contig_kernel(IirJobs jobs, IirGeo
       CausalState s0;
       float xa[K];
       xtile_get<W, K>(tile, lane, 0, xa);
-      if (t > 0) {
-        ck_load(ck, t, nl, line0, live ? lane : 0u, s0);
-        ck_load_x(ck, t, nl, line0, live ? lane : 0u, s0);
-      } else {
+      const bool head = t == 0;
+      if (head) {
         const double x0 = (double)xa[0];
         s0.x1 = s0.x2 = s0.x3 = x0;
         s0.y1 = s0.y2 = s0.y3 = s0.y4 = x0;
+      } else if constexpr (TURN) {
+        s0 = turn;
+      } else {
+        ck_load(ck, t, nl, line0, live ? lane : 0u, s0);
+        s0.x1 = (double)xa[2]; s0.x2 = (double)xa[1]; s0.x3 = (double)xa[0];
       }
-      const bool head = t == 0;
       double cz[K];
       const bool edge = head || (i0 + K + 4 > n);
       if (i1 < n) {
         const bool tail = i1 + K + 4 > n;
         CausalState s = s0;
-        causal_run_park<K>(s, xa, col, ce, i0, n, head);
+        if (head || TURN) {
+          causal_run_park<K>(s, xa, col, ce, i0, n, head);
+        } else {  // a complete tile behind the line start: its checkpoint is its first three causal values
+          col[0] = s0.y3; col[64] = s0.y2; col[128] = s0.y1;
+#pragma unroll
+          for (int j = 3; j < K; ++j) col[j * 64] = causal_step(s, (double)xa[j], ce);
+        }
         xtile_get<W, K>(tile, lane, 1, xb);
         causal_run<K, true>(s, xb, cz, ce, i1, n, tail);
         anti_run<K>(a, xb, cz, ce, i1, n, tail);
@@ -1287,7 +1291,6 @@ __global__ __launch_bounds__(256, 2) void iir_contig_kernel(IirJobs jobs, IirGeo
 
     // checkpoint of the tile in flight (steady tiles)
     double ny1 = 0.0, ny2 = 0.0, ny3 = 0.0, ny4 = 0.0;
-    float nx1 = 0.f, nx2 = 0.f, nx3 = 0.f;
     auto issue_ck = [&](int tt, uint32_t range) {
       const rsrc_t ry = make_rsrc_range(ck.y + ((int64_t)tt * 4) * nl + line0, range);
       const uint32_t sy = (uint32_t)nl * 8u;
@@ -1295,15 +1298,11 @@ __global__ __launch_bounds__(256, 2) void iir_contig_kernel(IirJobs jobs, IirGeo
       ny2 = ck_ld_f64(ry, lane * 8u, sy);
       ny3 = ck_ld_f64(ry, lane * 8u, 2u * sy);
       ny4 = ck_ld_f64(ry, lane * 8u, 3u * sy);
-      const rsrc_t rx = make_rsrc_range(ck.x + ((int64_t)tt * 3) * nl + line0, range);
-      const uint32_t sx = (uint32_t)nl * 4u;
-      nx1 = ck_ld_f32(rx, lane * 4u, 0u);
-      nx2 = ck_ld_f32(rx, lane * 4u, sx);
-      nx3 = ck_ld_f32(rx, lane * 4u, 2u * sx);
     };
     // steady tiles: away from both ends of the line, (t+1)W + 4 <= n and t >= 1
     const int t_hi = piped ? (int)((n - 4) / W) - 1 : -1;
-    int t = nt - 1;
+    plain_tile(nt - 1, std::true_type{});
+    int t = nt - 2;
     while (t >= 0 && !done) {
       if (t >= 1 && t <= t_hi) {
         // ---- tile t-1 and its checkpoint travel while tile t is computed ----
@@ -1314,14 +1313,15 @@ __global__ __launch_bounds__(256, 2) void iir_contig_kernel(IirJobs jobs, IirGeo
           commit_fill();
           CausalState s;
           s.y1 = ny1; s.y2 = ny2; s.y3 = ny3; s.y4 = ny4;
-          s.x1 = (double)nx1; s.x2 = (double)nx2; s.x3 = (double)nx3;
+          col[0] = ny3; col[64] = ny2; col[128] = ny1;  // the tile's first three causal values
           issue_fill(t - 1, 0xffffffffu);
           issue_ck(t - 1, mask_lt(1, t));  // tile 0 starts the line: no checkpoint
           float xa[K];
           double cz[K];
           xtile_get<W, K>(tile, lane, 0, xa);
+          s.x1 = (double)xa[2]; s.x2 = (double)xa[1]; s.x3 = (double)xa[0];
 #pragma unroll
-          for (int j = 0; j < K; ++j) col[j * 64] = causal_step(s, (double)xa[j], c);
+          for (int j = 3; j < K; ++j) col[j * 64] = causal_step(s, (double)xa[j], c);
           xtile_get<W, K>(tile, lane, 1, xb);
 #pragma unroll
           for (int j = 0; j < K; ++j) cz[j] = causal_step(s, (double)xb[j], c);
@@ -1337,7 +1337,7 @@ __global__ __launch_bounds__(256, 2) void iir_contig_kernel(IirJobs jobs, IirGeo
           --t;
         } while (t >= 1);
       } else {
-        plain_tile(t);
+        plain_tile(t, std::false_type{});
         --t;
       }
     }

@@ -51,8 +51,10 @@ constexpr int IIR_MAX_JOBS = 8;
 struct IirJob {
   const float *in;
   float *out;
-  double *ck_y;  // [npairs][4][nlines]: y[i-1..i-4] at the start of every second block
-  float *ck_x;   // [npairs][3][nlines]: x[i-1..i-3], contiguous-axis kernel only
+  // [npairs][4][nlines]: y[i+2..i-1] for the first sample i of every second block but the
+  // line's first and last -- the state three samples into the pair, whose x history is the
+  // pair's own first samples (iir_strided1_kernel: y[i-1..i-4] at the start of every block)
+  double *ck_y;
   // paired form (last pass of the normalized convolution): `in` is the numerator, `in2` the
   // denominator with its own checkpoint area, `out` receives numerator / denominator
   const float *in2;
