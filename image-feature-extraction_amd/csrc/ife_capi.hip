@@ -45,7 +45,8 @@ namespace {
   struct NS##_kernels {                                                                          \
     template <int K> static constexpr auto contig = NS::iir_contig_kernel<K>;                    \
     template <int K> static constexpr auto strided1 = NS::iir_strided1_kernel<K>;                \
-    template <int K, bool PAIRED> static constexpr auto strided = NS::iir_strided_kernel<K, PAIRED>; \
+    template <int K, bool PAIRED, bool BWD> static constexpr auto strided = NS::iir_strided_kernel<K, PAIRED, BWD>; \
+    template <int K, int S, typename TI, typename TM> static constexpr auto sweep_z = NS::iir_sweep_z_kernel<K, S, TI, TM>; \
     template <int K> static constexpr auto zslab_causal = NS::zslab_causal_kernel<K>;            \
     template <int K> static constexpr auto zslab_anti = NS::zslab_anti_kernel<K>;                \
     template <int K, int DIR> static constexpr auto zslab_fused = NS::zslab_fused_kernel<K, DIR>; \
@@ -131,12 +132,14 @@ struct ife_ctx {
   int fused_divide = 1;  // last axis pass stores numerator / denominator (sibling waves), not two fields
   int const_lines = 1;   // lines of one repeated 0 or 1 are copied, not filtered, where verified exact
   int feat_ring = 1;     // feature kernel: planes by LDS-DMA into a ring where the source is one float field
+  int z_sweep = 1;       // first axis pass: one causal sweep for all scales from image and mask, no prepass
   std::map<std::tuple<double, double, int64_t>, uint32_t> const_flags;  // (sigma, spacing, length) -> IirJob::const_lines
   // per scale slot: numerator ping/pong, denominator ping/pong (up to three scales run
   // through the line kernels together)
   DevBuf fld[IFE_MAX_SLOTS][4];
   DevBuf pre[2];  // image*certainty and certainty as float (prepass, shared by all scales)
   DevBuf ck_y[IIR_MAX_JOBS];  // one checkpoint area per concurrent job
+  DevBuf zs_rec;  // shared Z sweep: constant-line record per field and line (IirJob::line_rec)
   DevBuf st_img, st_mask, st_aux, st_out;  // HOST-mode staging
   // distance map: candidate stacks of the line passes (values, indices), the squared map and
   // the per-line partial sums of the expected distance
@@ -481,10 +484,21 @@ int ensure_slots(ife_ctx *ctx, const ife_volume_desc *v, int nslots) {
 // (jobs = numerator / denominator of up to three scales), each with its own sigma.
 // `in2` (strided axes, pair checkpoints only): jobs are PAIRED -- in[j] numerator, in2[j]
 // denominator, out[j] their quotient; job j uses checkpoint areas j and njobs + j.
+// `zs` (Z axis, pair checkpoints; jobs ordered scale-major, zs->nf fields per scale): the causal
+// sweeps of all jobs run first as ONE launch from the raw image and mask (iir_sweep_z_kernel,
+// which also leaves the sources in[] point at, unless !zs->write_src), and the line kernel
+// proper runs in its backward-only form.
+struct ZSweepSrc {
+  const void *img, *msk;  // msk null: no mask, one field
+  int img_dtype, msk_dtype;
+  float *tc, *cf;
+  int nf;
+  bool write_src;
+};
 int launch_iir(ife_ctx *ctx, const ife_volume_desc *v, int axis, int njobs,
                const float *const *in, float *const *out, const double *sigma,
                int in_y_chunks = 1, const int *order = nullptr /* per job: 0 (default), 1, 2 */,
-               const float *const *in2 = nullptr) {
+               const float *const *in2 = nullptr, const ZSweepSrc *zs = nullptr) {
   if (njobs < 1 || njobs > IIR_MAX_JOBS) return fail(ctx, IFE_E_ARG, "bad job count %d", njobs);
   IirGeom g = geom_for_axis(v, axis);
   if (in_y_chunks > 1) {
@@ -501,8 +515,13 @@ int launch_iir(ife_ctx *ctx, const ife_volume_desc *v, int axis, int njobs,
     return fail(ctx, IFE_E_SIZE, "volume too large for the 32-bit offsets of the line kernels");
   if (in2 && (axis == 0 || 2 * njobs > IIR_MAX_JOBS || ctx->iir_ckpt != 2))
     return fail(ctx, IFE_E_ARG, "the paired form runs on the strided axes with at most %d jobs", IIR_MAX_JOBS / 2);
+  if (zs && (axis != 2 || in2 || order || ctx->iir_ckpt != 2 || zs->nf < 1 || zs->nf > 2 || njobs % zs->nf ||
+             njobs / zs->nf > IFE_MAX_SLOTS || !zs->img || !zs->tc || (zs->nf == 2 && (!zs->msk || !zs->cf))))
+    return fail(ctx, IFE_E_ARG, "the shared sweep runs the Z pass of up to %d scales with pair checkpoints", IFE_MAX_SLOTS);
   int rc = ensure_ck(ctx, v, in2 ? 2 * njobs : njobs);
   if (rc) return rc;
+  if (zs && (rc = ensure(ctx, ctx->zs_rec, (size_t)zs->nf * (size_t)g.nlines * sizeof(uint32_t)))) return rc;
+  uint32_t any_const = 0;
   const double sp = axis == 0 ? v->sx : axis == 1 ? v->sy : v->sz;
   IirJobs jobs;
   memset(&jobs, 0, sizeof jobs);
@@ -535,27 +554,61 @@ int launch_iir(ife_ctx *ctx, const ife_volume_desc *v, int axis, int njobs,
       }
       jobs.j[j].const_lines = it->second;
     }
+    any_const |= jobs.j[j].const_lines;
+    if (zs) jobs.j[j].line_rec = (const uint32_t *)ctx->zs_rec.p + (size_t)(j % zs->nf) * (size_t)g.nlines;
   }
   g.njobs = njobs;
   g.ngroups = (int32_t)((g.nlines + (in2 ? 127 : 255)) / (in2 ? 128 : 256));  // paired: 128 lines x 2 fields
   const dim3 grid((unsigned)((g.ngroups + 7) / 8 * 8 * njobs), 1, 1);  // job-fastest, padded
+  const int sblock = ctx->iir_block ? ctx->iir_block : 12;
+  if (zs) {
+    // booked as `prep`: it stands where the prepass stood (13 B of sources per voxel) and one
+    // iir_z launch per step follows, as before
+    ProfScope pz(ctx, KK_PREP);
+    ZSweepArgs za;
+    za.img = zs->img; za.msk = zs->msk; za.tc = zs->tc; za.cf = zs->cf;
+    za.rec = (uint32_t *)ctx->zs_rec.p;
+    za.nf = zs->nf; za.write_src = zs->write_src ? 1 : 0; za.track = any_const ? 1 : 0;
+    IirGeom gs = g;
+    gs.njobs = zs->nf;  // workgroups: field-fastest within a run of eight line groups
+    const dim3 sgrid((unsigned)((gs.ngroups + 7) / 8 * 8 * zs->nf), 1, 1);
+    with_iir_kernels(ctx->iir_fma, [&](auto ks) {
+      using KS = decltype(ks);
+      with_const<8, 10, 12, 16>(sblock, [&](auto K) {
+        with_const<1, 2, 3>(njobs / zs->nf, [&](auto S) {
+          auto launch = [&](auto ti, auto tm) {
+            hipLaunchKernelGGL((KS::template sweep_z<decltype(K)::value, decltype(S)::value, decltype(ti), decltype(tm)>),
+                               sgrid, dim3(256), 0, ctx->stream, jobs, gs, za);
+          };
+          auto with_mask = [&](auto ti) {
+            if (zs->msk && zs->msk_dtype == IFE_U16) launch(ti, uint16_t{});
+            else launch(ti, uint8_t{});
+          };
+          if (zs->img_dtype == IFE_F32) with_mask(float{});
+          else with_mask(int16_t{});
+        });
+      });
+    });
+    IFE_HIP(ctx, hipGetLastError());
+  }
   ProfScope ps(ctx, axis == 2 ? KK_IIR_Z : axis == 1 ? KK_IIR_Y : KK_IIR_X);
   // register block of the strided axes: 12 for both (three waves per SIMD, 2.7 B of checkpoints
   // per sample).  Round 2 ran z with blocks of 10 for a fourth wave per SIMD; since the waits
   // are exact (iir_kernels.inc "Memory operations and waits") three waves hide the latency and
   // the fewer checkpoints win: z 1.85 -> 1.74 ms, y 1.87 with 12 against 2.06 with 16.
-  const int sblock = ctx->iir_block ? ctx->iir_block : 12;
   with_iir_kernels(ctx->iir_fma, [&](auto ks) {
     using KS = decltype(ks);
     auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, jobs, g); };
-    if (in2)
-      with_const<8, 10, 12, 16>(sblock, [&](auto K) { launch(KS::template strided<decltype(K)::value, true>); });
+    if (zs)
+      with_const<8, 10, 12, 16>(sblock, [&](auto K) { launch(KS::template strided<decltype(K)::value, false, true>); });
+    else if (in2)
+      with_const<8, 10, 12, 16>(sblock, [&](auto K) { launch(KS::template strided<decltype(K)::value, true, false>); });
     else if (axis == 0)
       with_const<8, 16>(ctx->iir_block, [&](auto K) { launch(KS::template contig<decltype(K)::value>); });
     else if (ctx->iir_ckpt == 1)
       with_const<8, 16>(ctx->iir_block, [&](auto K) { launch(KS::template strided1<decltype(K)::value>); });
     else
-      with_const<8, 10, 12, 16>(sblock, [&](auto K) { launch(KS::template strided<decltype(K)::value, false>); });
+      with_const<8, 10, 12, 16>(sblock, [&](auto K) { launch(KS::template strided<decltype(K)::value, false, false>); });
   });
   IFE_HIP(ctx, hipGetLastError());
   return IFE_OK;
@@ -663,7 +716,7 @@ int launch_prep(ife_ctx *ctx, const TI *img, const TM *msk, float *tc, float *cf
 // axis as ONE launch over all (scale, field) jobs.  Scale k of the group ends in slot k:
 // numerator in fld[k][0], denominator in fld[k][2].
 int smooth_group(ife_ctx *ctx, const float *src_num, const float *src_den,
-                 const ife_volume_desc *v, const double *sigmas, int nscales) {
+                 const ife_volume_desc *v, const double *sigmas, int nscales, const ZSweepSrc *zs = nullptr) {
   const int nf = src_den ? 2 : 1;
   const float *in[IIR_MAX_JOBS];
   float *out[IIR_MAX_JOBS];
@@ -683,7 +736,7 @@ int smooth_group(ife_ctx *ctx, const float *src_num, const float *src_den,
       }
   };
   fill(0, 0, true);                                    // Z: sources -> ping
-  rc = launch_iir(ctx, v, 2, nj, in, out, sg);
+  rc = launch_iir(ctx, v, 2, nj, in, out, sg, 1, nullptr, nullptr, zs);
   fill(0, 1, false);                                   // X: ping -> pong
   if (!rc) rc = launch_iir(ctx, v, 0, nj, in, out, sg);
   if (nf == 2 && ctx->fused_divide && ctx->iir_ckpt == 2) {
@@ -907,19 +960,33 @@ static int emphysema_typed(ife_ctx *ctx, const TI *img, const TM *msk, const ife
   // Cast + Multiply once for all scales (the reference redoes them per scale, a9).
   // mask == NULL: certainty == 1 everywhere, image*1 is the image and G(1) is exactly
   // 1.0f at every voxel (DESIGN.md "all-ones certainty"), so the denominator is skipped.
+  // IFE_OPT_Z_SWEEP: no prepass -- the first launch of the Z pass reads image and mask itself,
+  // leaves the same two sources and carries the causal recursions of all scales of a group
+  const bool sweep = ctx->z_sweep && ctx->iir_ckpt == 2;
+  ZSweepSrc zs;
+  zs.img = img; zs.msk = msk;
+  zs.img_dtype = std::is_same<TI, float>::value ? IFE_F32 : IFE_I16;
+  zs.msk_dtype = std::is_same<TM, uint16_t>::value ? IFE_U16 : IFE_U8;
+  zs.tc = tc; zs.cf = cf;
+  zs.nf = msk ? 2 : 1;
   const float *src_num;
   if (msk == nullptr && std::is_same<TI, float>::value) {
     src_num = reinterpret_cast<const float *>(img);
+    zs.write_src = false;  // the backward sweeps read the image
   } else {
-    int rc = launch_prep<TI, TM>(ctx, img, msk, tc, msk ? cf : nullptr, (int64_t)n);
-    if (rc) return rc;
+    if (!sweep) {
+      int rc = launch_prep<TI, TM>(ctx, img, msk, tc, msk ? cf : nullptr, (int64_t)n);
+      if (rc) return rc;
+    }
     src_num = tc;
+    zs.write_src = true;  // by the first group of scales
   }
   for (int s0 = 0; s0 < n_sigmas; s0 += IFE_MAX_SLOTS) {
     const int ns = std::min(IFE_MAX_SLOTS, n_sigmas - s0);
     double sg[IFE_MAX_SLOTS];
     for (int k = 0; k < ns; ++k) sg[k] = (double)sigmas[s0 + k];
-    int rc = smooth_group(ctx, src_num, msk ? cf : nullptr, vol, sg, ns);
+    int rc = smooth_group(ctx, src_num, msk ? cf : nullptr, vol, sg, ns, sweep ? &zs : nullptr);
+    zs.write_src = false;
     for (int k = 0; k < ns && !rc; ++k) {
       const bool q = slots_hold_quotient(ctx, msk != nullptr);
       const ValSmooth vs{(const float *)ctx->fld[k][0].p, msk && !q ? (const float *)ctx->fld[k][2].p : nullptr};
@@ -1026,7 +1093,7 @@ void ife_ctx_destroy(ife_ctx *ctx) {
   std::vector<DevBuf *> bufs = {&ctx->pre[0], &ctx->pre[1], &ctx->st_img, &ctx->st_mask,
                                 &ctx->st_aux, &ctx->st_out, &ctx->sc_out, &ctx->edt_g,
                                 &ctx->edt_i, &ctx->edt_d2, &ctx->edt_part, &ctx->dn_centres,
-                                &ctx->dn_ws, &ctx->dn_feat, &ctx->dj_ws};
+                                &ctx->dn_ws, &ctx->dn_feat, &ctx->dj_ws, &ctx->zs_rec};
   for (auto &sl : ctx->fld)
     for (auto &b : sl) bufs.push_back(&b);
   for (auto &b : ctx->ck_y) bufs.push_back(&b);
@@ -1080,6 +1147,9 @@ int ife_ctx_set_option(ife_ctx *ctx, int option, int value) {
       return IFE_OK;
     case IFE_OPT_FEAT_RING:
       ctx->feat_ring = value ? 1 : 0;
+      return IFE_OK;
+    case IFE_OPT_Z_SWEEP:
+      ctx->z_sweep = value ? 1 : 0;
       return IFE_OK;
     case IFE_OPT_DENSE_SCRATCH_MB:
       if (value < 0) return fail(ctx, IFE_E_ARG, "the dense scratch bound must be >= 0 MiB");

@@ -477,8 +477,12 @@ __device__ __forceinline__ void lds_workgroup_sync() {
 #ifndef IFE_IIR_FENCE
 #define IFE_IIR_FENCE 2  // recursion steps between scheduling fences in the steady iteration
 #endif
-template <int K, bool PAIRED = false>
+// BWD (first axis pass behind iir_sweep_z_kernel): no forward sweep here.  The checkpoints are
+// in place, the state in front of the last pair is read from that pair's checkpoint slot, and
+// the constant-line decision takes the forward half from the field's per-line record.
+template <int K, bool PAIRED = false, bool BWD = false>
 __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 : 1)) void iir_strided_kernel(IirJobs jobs, IirGeom g) {
+  static_assert(!(PAIRED && BWD), "the backward-only form is the plain form of the first axis pass");
   const IirBlock blk = iir_block_of(g, blockIdx.x);
   if (!blk.live) return;
   const IirJob &J = jobs.j[blk.job];
@@ -527,7 +531,7 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
   CausalState turn;
   turn.x1 = turn.x2 = turn.x3 = 0.0;
   turn.y1 = turn.y2 = turn.y3 = turn.y4 = 0.0;
-  {
+  if constexpr (!BWD) {
     float a0[K], a1[K], b0[K], b1[K];
     CausalState s;
     const int nfp = np - 1;
@@ -586,6 +590,18 @@ __global__ __launch_bounds__(256, K <= 10 ? 4 : (IFE_IIR_LDS_CZ && K <= 12 ? 3 :
       }
       if (p < nfp) run_pair(p, b0, b1);
       turn = s;
+    }
+  } else {
+    // left by the shared sweep: y1..y4 in the checkpoint slot of the last pair; the x history
+    // that belongs to them is the three samples in front of that pair
+    if (np > 1) {
+      ck_load(ck, np - 1, nl, Lw, cl, turn);
+      const auto B = src.at(wbase + ((int64_t)(2 * (np - 1) * K) - 3) * st);
+      turn.x3 = (double)src.ld(B, voff, 0u);
+      turn.x2 = (double)src.ld(B, voff, sst);
+      turn.x1 = (double)src.ld(B, voff, 2u * sst);
+      // ZSWEEP_NOT_CONST where a sample in front of the last pair differs from the first one
+      if (J.const_lines) fwd_ref = __builtin_bit_cast(float, J.line_rec[L]);
     }
   }
 
@@ -941,6 +957,246 @@ __global__ __launch_bounds__(256) void iir_strided1_kernel(IirJobs jobs, IirGeom
       sc.y1 = sn.y1; sc.y2 = sn.y2; sc.y3 = sn.y3; sc.y4 = sn.y4;
     }
   }
+}
+
+// ---------------------------------------------------------------------------------
+// Shared causal sweep of the first axis pass (Z), one launch in front of the backward-only
+// form of iir_strided_kernel.  All scales of a group filter the SAME two fields, so the causal
+// recursions of one line run side by side in one lane: every sample is loaded and converted
+// once, from the image and the mask themselves, and the prepass and its round trip through
+// memory go away.  A wave owns 64 x-adjacent lines of ONE field (workgroups are numbered
+// field-fastest through iir_block_of with njobs = fields, so the two fields of a line group
+// meet in one XCD's L2 for the mask): NS chains per lane, the x history shared between them,
+// and the denominator waves never read the image.  Per register block of K samples it
+//   * loads TI image and TM mask and forms t = float(image) * float(mask), c = float(mask)
+//     exactly as prep_kernel_* does (no mask: t = float(image), no multiply),
+//   * stores its field's value as the float source of the backward sweeps -- for EVERY sample
+//     of the line, the last (ragged) pair included, which is not recursed over,
+//   * advances the NS recursions; three samples into every pair 1 .. np-2 their y1..y4 go to
+//     the jobs' checkpoint areas (layout of ck_store), and after pair np-2 -- the state in
+//     front of the last pair -- to the slot of pair np-1, which no pair checkpoint uses,
+//   * where a job copies constant lines, compares every swept sample with the first and leaves
+//     the field's per-line record (IirJob::line_rec).
+// Every memory operation of the sweep is unconditional: a descriptor ends with the volume
+// (rows past the line end load zeros and drop their stores), and a field that is not read or
+// not written has an empty one.  A lane past the last line repeats the last line.
+// ---------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ uint32_t buf_ld_raw(rsrc_t r, uint32_t voff, uint32_t soff);
+template <>
+__device__ __forceinline__ uint32_t buf_ld_raw<float>(rsrc_t r, uint32_t voff, uint32_t soff) {
+  return __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0);
+}
+template <>
+__device__ __forceinline__ uint32_t buf_ld_raw<int16_t>(rsrc_t r, uint32_t voff, uint32_t soff) {
+  return (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, 0);
+}
+template <>
+__device__ __forceinline__ uint32_t buf_ld_raw<uint16_t>(rsrc_t r, uint32_t voff, uint32_t soff) {
+  return (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, 0);
+}
+template <>
+__device__ __forceinline__ uint32_t buf_ld_raw<uint8_t>(rsrc_t r, uint32_t voff, uint32_t soff) {
+  return (uint32_t)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(r, voff, soff, 0);
+}
+template <typename T>
+__device__ __forceinline__ float raw_as_f32(uint32_t r) {
+  if constexpr (std::is_same<T, float>::value) return __builtin_bit_cast(float, r);
+  else if constexpr (std::is_same<T, int16_t>::value) return (float)(int16_t)(uint16_t)r;
+  else return (float)r;
+}
+struct SweepY {
+  double y1, y2, y3, y4;
+};
+// causal_step with the x history outside the state (it is the same for every scale)
+template <typename C>
+__device__ __forceinline__ void sweep_step(SweepY &s, double x1, double x2, double x3, double xin, const C &c) {
+  const double a = IFE_MADD(x3, c.N3, IFE_MADD(x2, c.N2, IFE_MADD(x1, c.N1, xin * c.N0)));
+  const double t = IFE_MADD(s.y4, c.D4, IFE_MADD(s.y3, c.D3, IFE_MADD(s.y2, c.D2, s.y1 * c.D1)));
+  const double y = a - t;
+  s.y4 = s.y3; s.y3 = s.y2; s.y2 = s.y1; s.y1 = y;
+}
+struct SweepCoef {
+  double N0, N1, N2, N3, D1, D2, D3, D4;
+};
+template <int K, int NS, typename TI, typename TM>
+__global__ __launch_bounds__(256, K <= 12 ? 4 : 3) void iir_sweep_z_kernel(IirJobs jobs, IirGeom g, ZSweepArgs a) {
+  const IirBlock blk = iir_block_of(g, blockIdx.x);  // g.njobs = fields: blk.job is the field
+  if (!blk.live) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  const int64_t Lw = uniform64((int64_t)blk.group * blockDim.x + (int64_t)(threadIdx.x & ~63u));
+  if (Lw >= g.nlines) return;  // wave-uniform
+  const uint32_t f = blk.job, nf = (uint32_t)a.nf;
+  const bool is_den = f != 0u;
+  const bool has_mask = a.msk != nullptr;
+  // Z axis: line L starts at element L, samples are nl elements apart
+  const int64_t n = g.n, nl = g.nlines;
+  int64_t L = Lw + lane;
+  if (L >= nl) L = nl - 1;  // a lane past the last line repeats the last line
+  const uint32_t cl = (uint32_t)(L - Lw);
+  const uint32_t sst = (uint32_t)nl;  // 2K*nl*4 < 2^31 is checked on the host
+  const int nb = (int)((n + K - 1) / K);
+  const int np = (nb + 1) / 2;
+  const int nfp = np - 1;  // complete pairs in front of the last one: the swept part of the line
+  float *const dst = reinterpret_cast<float *>(uniform64(reinterpret_cast<int64_t>(is_den ? a.cf : a.tc)));
+  // all ones / zero, as integers (mask_lt's comment): which streams this wave really moves
+  const uint32_t rd_img = is_den ? 0u : 0xffffffffu;
+  const uint32_t rd_msk = has_mask ? 0xffffffffu : 0u;
+  const uint32_t wr_src = a.write_src != 0 ? 0xffffffffu : 0u;
+
+  SweepCoef c[NS];
+  double *cky[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    const IirJob &J = jobs.j[(uint32_t)k * nf + f];
+    c[k] = SweepCoef{J.c.N0, J.c.N1, J.c.N2, J.c.N3, J.c.D1, J.c.D2, J.c.D3, J.c.D4};
+    cky[k] = J.ck_y;
+  }
+
+  uint32_t ri[K], rm[K];  // the next register block of raw image and mask, in flight
+  float v[K];
+  SweepY s[NS];
+  double x1 = 0.0, x2 = 0.0, x3 = 0.0;
+  bool cst = true;
+  uint32_t ref = 0u;
+
+  // Descriptors are rebuilt for every G rows (three scalar offsets per element size instead of
+  // K - 1).  Their range, in 32-bit scalar integer arithmetic: the elements from lane 0's
+  // sample in row `row` to the end of the volume, of at most 2K rows (more is never reached
+  // from one base, and 2K * nl * 4 < 2^31), nothing from the line's end on.
+  constexpr int G = K % 4 == 0 ? 4 : 2;
+  const int ni = (int)n;
+  const uint32_t nlu = (uint32_t)nl, lwu = (uint32_t)Lw;  // Lw < nl < 2^26
+  auto range_of = [&](int row, uint32_t esize) -> uint32_t {
+    int rows = ni - row;
+    rows = rows < 0 ? 0 : rows;
+    rows = rows > 2 * K ? 2 * K : rows;
+    const uint32_t one = rows > 0 ? 1u : 0u;  // s_min: no lane mask
+    return ((uint32_t)rows * nlu - one * lwu) * esize;
+  };
+  auto load_blk = [&](int b, uint32_t (&ri)[K], uint32_t (&rm)[K]) {
+    __builtin_amdgcn_sched_barrier(0);  // behind the conversions that free these registers
+#pragma unroll
+    for (int q = 0; q < K; q += G) {
+      const int row = b * K + q;
+      const int64_t e0 = Lw + (int64_t)row * nl;
+      const rsrc_t dI = make_rsrc_range(static_cast<const TI *>(a.img) + e0, range_of(row, sizeof(TI)) & rd_img);
+#pragma unroll
+      for (int j = 0; j < G; ++j)
+        ri[q + j] = buf_ld_raw<TI>(dI, cl * (uint32_t)sizeof(TI), (uint32_t)j * sst * (uint32_t)sizeof(TI));
+    }
+#pragma unroll
+    for (int q = 0; q < K; q += G) {
+      const int row = b * K + q;
+      const int64_t e0 = Lw + (int64_t)row * nl;
+      const rsrc_t dM = make_rsrc_range(static_cast<const TM *>(has_mask ? a.msk : a.img) + e0,
+                                        range_of(row, sizeof(TM)) & rd_msk);
+#pragma unroll
+      for (int j = 0; j < G; ++j)
+        rm[q + j] = buf_ld_raw<TM>(dM, cl * (uint32_t)sizeof(TM), (uint32_t)j * sst * (uint32_t)sizeof(TM));
+    }
+  };
+  // raw -> this wave's field, and its source rows for the backward sweeps
+  auto take_blk = [&](int b, const uint32_t (&ri)[K], const uint32_t (&rm)[K]) {
+    // (scheduling fence: left alone, the conversions move up into the recursion in front of
+    // them, and with them the wait for loads that were issued a moment ago)
+    __builtin_amdgcn_sched_barrier(0);
+    if (is_den) {  // uniform branches over arithmetic only
+#pragma unroll
+      for (int j = 0; j < K; ++j) v[j] = raw_as_f32<TM>(rm[j]);
+    } else if (has_mask) {
+#pragma unroll
+      for (int j = 0; j < K; ++j) v[j] = raw_as_f32<TI>(ri[j]) * raw_as_f32<TM>(rm[j]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < K; ++j) v[j] = raw_as_f32<TI>(ri[j]);
+    }
+#pragma unroll
+    for (int q = 0; q < K; q += G) {
+      const int row = b * K + q;
+      const rsrc_t dO = make_rsrc_range(dst + Lw + (int64_t)row * nl, range_of(row, 4u) & wr_src);
+#pragma unroll
+      for (int j = 0; j < G; ++j) buf_st_f32(dO, cl * 4u, (uint32_t)j * sst * 4u, v[q + j]);
+    }
+  };
+  auto track = [&]() {
+    if (a.track) {  // uniform
+#pragma unroll
+      for (int j = 0; j < K; ++j) cst = cst && __builtin_bit_cast(uint32_t, v[j]) == ref;
+    }
+  };
+  auto run = [&](int j0, int j1) {
+#pragma unroll
+    for (int j = j0; j < j1; ++j) {
+      const double xin = (double)v[j];
+#pragma unroll
+      for (int k = 0; k < NS; ++k) sweep_step(s[k], x1, x2, x3, xin, c[k]);
+      x3 = x2; x2 = x1; x1 = xin;
+    }
+  };
+  auto store_state = [&](int slot) {
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      // (made scalar by hand: a base the compiler has parked in a vector register turns every
+      // store into a loop over "distinct" descriptors, and all wait counts around it to zero)
+      double *const base = reinterpret_cast<double *>(uniform64(reinterpret_cast<int64_t>(cky[k])));
+      const rsrc_t ry = IFE_CK_RSRC(base + ((int64_t)slot * 4) * nl + Lw);
+      const uint32_t sy = (uint32_t)nl * 8u;
+      ck_st_f64(ry, cl * 8u, 0u, s[k].y1);
+      ck_st_f64(ry, cl * 8u, sy, s[k].y2);
+      ck_st_f64(ry, cl * 8u, 2u * sy, s[k].y3);
+      ck_st_f64(ry, cl * 8u, 3u * sy, s[k].y4);
+    }
+  };
+
+  // One block ahead: a block is converted (take_blk) and the next one requested into the same
+  // registers before the recursion runs over it -- 45 double operations per sample and scale
+  // group of latency cover, at four waves per SIMD where K <= 12.
+  load_blk(0, ri, rm);
+  if (nfp > 0) {
+    // pair 0: border form on the first block (causal_step_edge, each scale with its own
+    // border coefficients), then the interior form
+    take_blk(0, ri, rm);
+    load_blk(1, ri, rm);
+    ref = __builtin_bit_cast(uint32_t, v[0]);
+    {
+      const double e0 = (double)v[0];
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        const IirCoef ce = edge_coefs((uint32_t)k * nf + f);
+        CausalState e;
+        e.x1 = e.x2 = e.x3 = e0;
+        e.y1 = e.y2 = e.y3 = e.y4 = e0;
+#pragma unroll
+        for (int j = 0; j < K; ++j) causal_step_edge(e, (double)v[j], ce, j);
+        s[k] = SweepY{e.y1, e.y2, e.y3, e.y4};
+      }
+      x1 = (double)v[K - 1]; x2 = (double)v[K - 2]; x3 = (double)v[K - 3];
+    }
+    track();
+    take_blk(1, ri, rm);
+    load_blk(2, ri, rm);
+    run(0, K);
+    track();
+    for (int p = 1; p < nfp; ++p) {
+      take_blk(2 * p, ri, rm);
+      load_blk(2 * p + 1, ri, rm);
+      run(0, 3);
+      store_state(p);  // three samples into the pair (ck_store)
+      run(3, K);
+      track();
+      take_blk(2 * p + 1, ri, rm);
+      load_blk(2 * p + 2, ri, rm);
+      run(0, K);
+      track();
+    }
+    store_state(np - 1);  // the state in front of the last pair
+    if (a.track) a.rec[(int64_t)f * nl + L] = cst ? ref : ZSWEEP_NOT_CONST;
+  }
+  // the last pair: sources only (its second block may lie past the line end: nothing moves)
+  take_blk(2 * nfp, ri, rm);
+  load_blk(2 * nfp + 1, ri, rm);
+  take_blk(2 * nfp + 1, ri, rm);
 }
 
 // =================================================================================

@@ -63,10 +63,29 @@ struct IirJob {
   // constant the host found this filter to make of it (ife_capi.hip const_line_flags): bit 0:
   // +0 -> +0, bit 1: 1.0f -> 1.0f, bit 2: -0 -> -0, bit 3: -0 -> +0; 0 = always filter
   uint32_t const_lines;
+  // backward-only form of the strided kernel (Z pass behind iir_sweep_z_kernel): the per-line
+  // record of this job's FIELD -- the bit pattern of the line's first sample if every sample in
+  // front of the last pair equals it, else ZSWEEP_NOT_CONST -- read where const_lines != 0
+  const uint32_t *line_rec;
   IirCoef c;
 };
 struct IirJobs {
   IirJob j[IIR_MAX_JOBS];
+};
+
+// ---- shared causal sweep of the first axis pass (iir_sweep_z_kernel) ----------------------
+// The jobs of the launch are (scale k, field f) at index k * nf + f, as smooth_group orders them.
+// A quiet NaN with a payload: no constant that const_line_response accepts
+constexpr uint32_t ZSWEEP_NOT_CONST = 0x7fc00001u;
+struct ZSweepArgs {
+  const void *img;   // TI, read by the numerator waves
+  const void *msk;   // TM, or null: certainty one, no denominator waves
+  float *tc, *cf;    // sources of the backward sweeps: float(image) * float(mask), float(mask) (cf: with a mask)
+  uint32_t *rec;     // [nf][nlines] constant-line records, written where `track`
+  int32_t nf;        // fields: 2 with a mask, else 1
+  int32_t write_src; // 0: nothing is stored -- the sources are in place already (a later group of
+                     // scales), or the backward sweeps read the float image itself (no mask)
+  int32_t track;     // some job has const_lines != 0
 };
 
 // ---- Z pass of a Z-slab (multi-GPU): the recursion state crosses the slab boundary -------

@@ -110,7 +110,14 @@ typedef enum {
    * in ife_bag_image_dense, the features of a group of scales): 0 (default) sizes the groups
    * from the free device memory.  Bins and scales then go through in smaller groups; results
    * never change. */
-  IFE_OPT_DENSE_SCRATCH_MB = 11
+  IFE_OPT_DENSE_SCRATCH_MB = 11,
+  /* 1 (default): the first axis pass (Z) of ife_emphysema_features and of its streaming form
+   * runs ONE causal sweep per line for all scales of a group, straight from image and mask (no
+   * cast / multiply prepass; that launch also leaves the two float sources), and the line
+   * kernel proper then makes backward sweeps only.  In force with IFE_OPT_IIR_CKPT 2.  0: the
+   * prepass, and every (scale, field) job sweeps forward on its own.  Same results bit for
+   * bit. */
+  IFE_OPT_Z_SWEEP = 12
 } ife_option;
 
 typedef struct {

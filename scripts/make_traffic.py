@@ -64,9 +64,9 @@ def kind_of(name):
         return "features"
     if "iir_contig" in name:
         return "iir_x"
-    if "iir_strided_kernel" in name:
-        return "iir_y" if ", true>" in name else "iir_z"
-    if "prep_kernel" in name:
+    if "iir_strided_kernel" in name:  # <K, PAIRED[, BWD]>
+        return "iir_y" if re.search(r"iir_strided_kernel<\d+, true", name) else "iir_z"
+    if "prep_kernel" in name or "iir_sweep_z_kernel" in name:  # the sweep is booked where the prepass stood
         return "prep"
     return None
 
