@@ -7,6 +7,9 @@ algorithm under test: brute-force min-plus, no envelopes, no ballots.
             h(i) = float64(i) * spacing, every operation rounded on its own; DBL_MAX where the
             volume has no contour voxel
 
+sq_dist(..., slabs=True) is the same arithmetic one slab at a time, for lines of a few hundred voxels;
+expected_distance_device_order sums the terms of ife_expected_distance in the device's order.
+
 Volumes are [z, y, x]; spacing is (sx, sy, sz)."""
 import numpy as np
 
@@ -42,14 +45,27 @@ def _minplus(g, h, axis):
     return np.ascontiguousarray(np.moveaxis(out, -1, axis))
 
 
-def sq_dist(site, spacing=(1.0, 1.0, 1.0)):
-    """Separable form: x, then y, then z, the order in which D2 accumulates its terms."""
+def _minplus_slabs(g, h, axis):
+    """_minplus one slab of the leading axis at a time: the same sums and the same minimum, with an
+    [n, n] temporary per line of one slab instead of the whole volume (lines of a few hundred)."""
+    g = np.moveaxis(g, axis, -1)
+    d = (h[:, None] - h[None, :]) ** 2                      # [j, i]
+    out = np.empty(g.shape, np.float64)
+    for k in range(g.shape[0]):
+        out[k] = np.min(g[k][..., :, None] + d, axis=-2)
+    return np.ascontiguousarray(np.moveaxis(out, -1, axis))
+
+
+def sq_dist(site, spacing=(1.0, 1.0, 1.0), slabs=False):
+    """Separable form: x, then y, then z, the order in which D2 accumulates its terms.  `slabs`:
+    slab by slab (_minplus_slabs), for volumes whose lines are too long for one temporary."""
     site = np.asarray(site, bool)
     hx, hy, hz = _coords(site.shape, spacing)
+    minplus = _minplus_slabs if slabs else _minplus
     g = np.where(site, 0.0, DBL_MAX)
-    g = _minplus(g, hx, 2)
-    g = _minplus(g, hy, 1)
-    return _minplus(g, hz, 0)
+    g = minplus(g, hx, 2)
+    g = minplus(g, hy, 1)
+    return minplus(g, hz, 0)
 
 
 def sq_dist_allpairs(site, spacing=(1.0, 1.0, 1.0)):
@@ -64,14 +80,48 @@ def sq_dist_allpairs(site, spacing=(1.0, 1.0, 1.0)):
     return out
 
 
-def signed_distance_map(mask, spacing=(1.0, 1.0, 1.0), inside_is_positive=True, squared=False):
+def signed_distance_map(mask, spacing=(1.0, 1.0, 1.0), inside_is_positive=True, squared=False, slabs=False):
     fg = np.asarray(mask) != 0
-    d2 = sq_dist(contour(fg), spacing)
+    d2 = sq_dist(contour(fg), spacing, slabs)
     val = d2 if squared else np.sqrt(d2)
     return np.where(fg == bool(inside_is_positive), val, -val)
 
 
-def expected_distance_terms(mask, prob, spacing=(1.0, 1.0, 1.0)):
-    """The terms out(v) * prob(v) of the foreground voxels, in raster order."""
+def expected_distance_terms(mask, prob, spacing=(1.0, 1.0, 1.0), slabs=False, dist=None):
+    """The terms out(v) * prob(v) of the foreground voxels, in raster order.  `dist`: the map
+    signed_distance_map(mask, spacing), where the caller has it already."""
     fg = np.asarray(mask) != 0
-    return (signed_distance_map(mask, spacing)[fg] * np.asarray(prob, np.float64)[fg])
+    if dist is None:
+        dist = signed_distance_map(mask, spacing, slabs=slabs)
+    return (dist[fg] * np.asarray(prob, np.float64)[fg])
+
+
+REDUCE_THREADS = 256   # EDT_REDUCE_THREADS of csrc/distance_kernels.hpp
+
+
+def expected_distance_device_order(mask, prob, spacing=(1.0, 1.0, 1.0), slabs=False, dist=None):
+    """(mean, count) with the sum built in the order csrc/distance_kernels.hpp documents, every
+    step an IEEE double operation: per z line the terms sqrt(D2) * prob of its foreground voxels in
+    line order onto 0.0; thread t of 256 adds the sums of lines t, t + 256, ... in that order; the
+    256 partial sums go through a binary tree (s[t] += s[t + o] for o = 128, 64, ... 1); sum / count.
+    `dist` as in expected_distance_terms (only its foreground, where it is sqrt(D2), is read)."""
+    fg = np.asarray(mask) != 0
+    prob = np.asarray(prob, np.float64)
+    if dist is None:
+        dist = np.sqrt(sq_dist(contour(fg), spacing, slabs))
+    nz = fg.shape[0]
+    line = np.zeros(fg.shape[1:], np.float64)
+    for z in range(nz):
+        line = np.where(fg[z], line + dist[z] * prob[z], line)
+    line = line.ravel()                                    # line number: x fastest, then y
+    pad = -line.size % REDUCE_THREADS                      # s + 0.0 == s for the s >= +0.0 here
+    rows = np.concatenate([line, np.zeros(pad)]).reshape(-1, REDUCE_THREADS)
+    part = np.zeros(REDUCE_THREADS, np.float64)
+    for r in rows:
+        part = part + r
+    o = REDUCE_THREADS // 2
+    while o > 0:
+        part[:o] = part[:o] + part[o:2 * o]
+        o //= 2
+    n = int(np.count_nonzero(fg))
+    return (float(part[0] / np.float64(n)) if n else 0.0), n

@@ -28,6 +28,40 @@ def test_oracle_forms_agree(density, spacing):
     assert np.array_equal(E.sq_dist(site, spacing), E.sq_dist_allpairs(site, spacing))
 
 
+@pytest.mark.parametrize("shape,density,seed", [((66, 70, 33), 0.3, 3), ((7, 9, 130), 0.5, 2)])
+@pytest.mark.parametrize("spacing", [(1.0, 1.0, 1.0), (0.7, 0.7, 2.5)])
+def test_oracle_slab_form_gives_the_same_bits(shape, density, seed, spacing):
+    """The slab-wise min-plus (for lines too long for one temporary) is the same arithmetic: two of
+    the masks of tests/test_gpu_distance.py ("yz_d0.3", "x130"), bit for bit."""
+    mask = (np.random.default_rng(seed).random(shape) < density).astype(np.uint8)
+    site = E.contour(mask != 0)
+    whole, slabs = E.sq_dist(site, spacing), E.sq_dist(site, spacing, slabs=True)
+    assert whole.tobytes() == slabs.tobytes()
+    assert E.signed_distance_map(mask, spacing, slabs=True).tobytes() == E.signed_distance_map(mask, spacing).tobytes()
+
+
+def test_oracle_device_order_sum_is_within_the_bound_of_the_exact_sum():
+    """The numpy replica of the device's summation order (edt_oracle.expected_distance_device_order)
+    against math.fsum of the same terms: n additions of non-negative terms, each rounding at most
+    2^-53 of the running sum, and one division; the bound of tests/test_gpu_distance.py.  More than
+    256 lines, no multiple of 256, and lines without foreground."""
+    import math
+    shape = (5, 23, 37)                              # 851 z lines: threads with 3 and with 4 lines
+    rng = np.random.default_rng(31)
+    mask = ((rng.random(shape) < 0.6) * 3).astype(np.uint8)
+    mask[:, 4, :] = 0
+    prob = rng.random(shape)
+    terms = E.expected_distance_terms(mask, prob)
+    n = int(np.count_nonzero(mask))
+    want = math.fsum(terms) / n
+    got, got_n = E.expected_distance_device_order(mask, prob)
+    assert got_n == n == terms.size
+    assert abs(got - want) <= 2 * n * 2.0 ** -53 * want
+    assert E.expected_distance_device_order(mask, prob, slabs=True) == (got, n)
+    assert E.expected_distance_device_order(mask, prob, dist=E.signed_distance_map(mask)) == (got, n)
+    assert E.expected_distance_device_order(np.zeros(shape, np.uint8), prob) == (0.0, 0)
+
+
 def test_oracle_contour_and_empty():
     fg = np.zeros((5, 6, 7), bool)
     fg[1:4, 1:5, 1:6] = True                      # 3 x 4 x 5 box: only the centre 1 x 2 x 3 is interior

@@ -6,7 +6,11 @@ Bars: everything up to the jet, the smoothed value S and the gradient magnitude 
 IEEE operations on the same operands in the same order on both sides (both built with
 -ffp-contract=off), so they are compared as floats for equality, NaN and Inf positions included.
 The eigenvalue components carry the bars of the finite-difference path: 1e-6 |lambda_1| in trig
-mode 0 (tests/test_gpu_parity.py), 2e-6 in the library's default mode (tests/test_gpu_trig_default.py)."""
+mode 0 (tests/test_gpu_parity.py), 2e-6 in the library's default mode (tests/test_gpu_trig_default.py).
+
+The pointwise pass picks its form from pointer alignment and n % 4 (csrc/diff_capi.inc launch_jet):
+the cases with device pointers off the vector grid and with n % 4 != 0 reach the scalar kernels and
+the element-wise planar stores; volumes beyond one grid are in tests/test_gpu_large_grids.py."""
 import os
 import subprocess
 import sys
@@ -181,6 +185,169 @@ def test_smaller_volume_after_a_larger_one_sees_no_stale_workspace(ctx, oracle, 
     smask[:, :, :3] = 0
     got = ctx.differential_features(small, smask, [1.5], SPACING)[0]
     _assert_features(got, jet_oracle.features(oracle, small, smask, 1.5, SPACING), smask, TOL_MODE0, "small volume")
+
+
+# ---- the forms of the pointwise pass (launch_jet: pointer alignment and n % 4) --------------------
+def _weights(shape, dtype, seed):
+    """A third exact zeros; the value is the certainty weight (1 and 2, or 1 and 300 in 16 bits)."""
+    values = np.array([0, 1, 2] if dtype == np.uint8 else [0, 1, 300], dtype)
+    return values[np.random.default_rng(seed).integers(0, 3, shape)]
+
+
+@pytest.mark.parametrize("mdt", [np.uint8, np.uint16])
+@pytest.mark.parametrize("shape", [(5, 7, 9), (9, 10, 11)])
+def test_differential_features_planar_with_a_scalar_tail(ctx, ife, oracle, shape, mdt):
+    """n % 4 != 0: the vec4 kernel leaves a tail to the scalar one, and the component planes do not
+    start on 16-byte boundaries (pvec false: planar stores element by element)."""
+    n = shape[0] * shape[1] * shape[2]
+    assert n % 4 != 0 and n // 4 > 0
+    img, mask, sigmas = _image(shape, 12), _weights(shape, mdt, 13), (0.8, 1.5)
+    inter = ctx.differential_features(img, mask, sigmas, SPACING)
+    planar = ctx.differential_features(img, mask, sigmas, SPACING, layout=ife.PLANAR)
+    assert planar.shape == (2, 8) + shape
+    np.testing.assert_array_equal(np.moveaxis(planar, 1, -1).view(np.uint32), inter.view(np.uint32))
+    for s, sigma in enumerate(sigmas):
+        # the entry point takes its sigmas as floats: the oracle gets the float's value (0.8 is none)
+        ref = jet_oracle.features(oracle, img, mask, float(np.float32(sigma)), SPACING)
+        _assert_features(np.ascontiguousarray(np.moveaxis(planar[s], 0, -1)), ref, mask, TOL_MODE0,
+                         "planar %s sigma %g" % (np.dtype(mdt).name, sigma))
+
+
+def _device_at(array, offset_bytes):
+    """(tensor to keep alive, pointer): `array` in device memory, `offset_bytes` past a 16-byte
+    boundary."""
+    import torch
+    raw = np.ascontiguousarray(array).view(np.uint8).reshape(-1)
+    buf = torch.zeros(raw.size + 16, dtype=torch.uint8, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    buf[offset_bytes:offset_bytes + raw.size].copy_(torch.from_numpy(raw))
+    return buf, buf.data_ptr() + offset_bytes
+
+
+DEVICE_SHAPES = [(9, 10, 11), (12, 20, 24)]   # n % 4 == 2 (a tail) and n % 4 == 0
+
+
+@pytest.mark.parametrize("shape", DEVICE_SHAPES)
+def test_differential_features_planar_output_off_the_16_byte_grid(ctx, ife, shape):
+    """Planar output 4 bytes past a 16-byte boundary (allowed): the vec4 kernel with pvec false."""
+    import torch
+    img, mask, sigmas = _image(shape, 14), _weights(shape, np.uint8, 15), (1.0, 2.0)
+    host = ctx.differential_features(img, mask, sigmas, SPACING, layout=ife.PLANAR)
+    (k_img, p_img), (k_mask, p_mask) = _device_at(img, 0), _device_at(mask, 0)
+    d_out = torch.full((host.size + 4,), float("nan"), dtype=torch.float32, device="cuda")
+    assert (d_out.data_ptr() + 4) % 16 == 4
+    torch.cuda.synchronize()
+    ctx.differential_features_device(p_img, ife.F32, p_mask, ife.U8, shape, SPACING, sigmas, d_out.data_ptr() + 4,
+                                     layout=ife.PLANAR)
+    ctx.synchronize()
+    got = d_out.cpu().numpy()
+    np.testing.assert_array_equal(got[1:1 + host.size].view(np.uint32), host.reshape(-1).view(np.uint32))
+    assert np.isnan(got[0]) and np.isnan(got[1 + host.size:]).all()      # nothing beside the output
+
+
+@pytest.mark.parametrize("img_off,mask_off", [(2, 0), (0, 2), (2, 2)], ids=["image", "mask", "both"])
+@pytest.mark.parametrize("layout", ["interleaved", "planar"])
+@pytest.mark.parametrize("shape", DEVICE_SHAPES)
+def test_differential_features_16_bit_inputs_off_the_vector_grid(ctx, ife, synth, shape, layout, img_off, mask_off):
+    """int16 image and uint16 mask 2 bytes past a 16-byte boundary: aligned to their element, not to
+    four of them, so the prepass (image or mask) and the pointwise pass (mask) take their scalar
+    kernels for the whole volume."""
+    import torch
+    lay = ife.PLANAR if layout == "planar" else ife.INTERLEAVED
+    img, mask, sigmas = synth.volume_i16(shape, 16), _weights(shape, np.uint16, 17), (1.5,)
+    host = ctx.differential_features(img, mask, sigmas, SPACING, layout=lay)
+    (k_img, p_img), (k_mask, p_mask) = _device_at(img, img_off), _device_at(mask, mask_off)
+    assert p_img % 8 == img_off and p_mask % 8 == mask_off
+    d_out = torch.full(host.shape, float("nan"), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    ctx.differential_features_device(p_img, ife.I16, p_mask, ife.U16, shape, SPACING, sigmas, d_out.data_ptr(),
+                                     layout=lay)
+    ctx.synchronize()
+    np.testing.assert_array_equal(d_out.cpu().numpy().view(np.uint32), host.view(np.uint32))
+
+
+@pytest.mark.parametrize("shape", DEVICE_SHAPES)
+def test_jet_output_8_bytes_past_a_16_byte_boundary(ctx, ife, shape):
+    """Ten floats per voxel go out as 8-byte stores: 8 bytes past a 16-byte boundary is allowed."""
+    import torch
+    img, cert, sigma = _image(shape, 18), _certainty(shape, 19), 1.5
+    host = ctx.normalized_convolution_jet(img, cert, sigma, SPACING)
+    (k_img, p_img), (k_cert, p_cert) = _device_at(img, 0), _device_at(cert, 0)
+    d_out = torch.full((host.size + 4,), float("nan"), dtype=torch.float32, device="cuda")
+    assert (d_out.data_ptr() + 8) % 16 == 8
+    torch.cuda.synchronize()
+    ctx.normalized_convolution_jet_device(p_img, p_cert, shape, SPACING, sigma, d_out.data_ptr() + 8)
+    ctx.synchronize()
+    got = d_out.cpu().numpy()
+    np.testing.assert_array_equal(got[2:2 + host.size].view(np.uint32), host.reshape(-1).view(np.uint32))
+    assert np.isnan(got[:2]).all() and np.isnan(got[2 + host.size:]).all()
+
+
+# ---- derivative coefficients through the other line kernels ------------------------------------
+class _Options:
+    """Options for one block, then the library's defaults again."""
+    DEFAULTS = {"OPT_IIR_BLOCK": 0, "OPT_IIR_CKPT": 2}
+
+    def __init__(self, ctx, ife, **opts):
+        self.ctx, self.ife, self.opts = ctx, ife, opts
+
+    def __enter__(self):
+        for k, v in self.opts.items():
+            self.ctx.set_option(getattr(self.ife, k), v)
+
+    def __exit__(self, *a):
+        for k in self.opts:
+            self.ctx.set_option(getattr(self.ife, k), self.DEFAULTS[k])
+
+
+# register blocks of 8 (x: contig<8>, y and z: strided<8>) and of 16 (strided<16>), and a checkpoint
+# in front of every block (y and z: strided1)
+LINE_OPTIONS = [{"OPT_IIR_BLOCK": 8}, {"OPT_IIR_BLOCK": 16}, {"OPT_IIR_CKPT": 1}]
+LINE_IDS = ["block8", "block16", "ckpt1"]
+ORDER_SHAPE, ORDER_SIGMAS = (25, 49, 65), (0.8, 2.5)
+_order_refs = {}
+
+
+def _order_case(oracle):
+    """(volume, {(sigma, axis, order): the oracle's pass}); computed once and shared."""
+    if not _order_refs:
+        vol = _image(ORDER_SHAPE, 5)
+        _order_refs["vol"] = vol
+        _order_refs["want"] = {(sigma, axis, order): jet_oracle.recursive_gaussian_axis_order(oracle, vol, axis, sigma,
+                                                                                            SPACING, order)
+                               for sigma in ORDER_SIGMAS for axis in range(3) for order in (1, 2)}
+    return _order_refs["vol"], _order_refs["want"]
+
+
+@pytest.mark.parametrize("opts", LINE_OPTIONS, ids=LINE_IDS)
+def test_recursive_gaussian_orders_under_line_options(ctx, ife, oracle, opts):
+    import torch
+    vol, want = _order_case(oracle)
+    d_in = torch.from_numpy(vol).cuda()
+    d_out = torch.empty_like(d_in)
+    with _Options(ctx, ife, **opts):
+        for (sigma, axis, order), ref in want.items():
+            d_out.fill_(float("nan"))
+            torch.cuda.synchronize()
+            ctx.stage_recursive_gaussian_order(d_in.data_ptr(), d_out.data_ptr(), ORDER_SHAPE, SPACING, axis, sigma,
+                                               order)
+            ctx.synchronize()
+            np.testing.assert_array_equal(d_out.cpu().numpy(), ref,
+                                          "%r sigma %g axis %d order %d" % (opts, sigma, axis, order))
+
+
+_jet_ref = {}
+
+
+@pytest.mark.parametrize("opts", LINE_OPTIONS, ids=LINE_IDS)
+def test_jet_under_line_options(ctx, ife, oracle, opts):
+    shape, sigma = (12, 70, 67), 2.5
+    img, cert = _image(shape, 7), _certainty(shape, 8)
+    if not _jet_ref:
+        _jet_ref["want"] = jet_oracle.jet(oracle, img, cert, sigma, SPACING)
+    with _Options(ctx, ife, **opts):
+        got = ctx.normalized_convolution_jet(img, cert, sigma, SPACING)
+    np.testing.assert_array_equal(got, _jet_ref["want"])
 
 
 # ---- arguments ------------------------------------------------------------------------------------
