@@ -31,6 +31,7 @@ OPT_CONST_LINES = 9
 OPT_FEAT_RING = 10
 OPT_DENSE_SCRATCH_MB = 11
 OPT_Z_SWEEP = 12
+BAG_COUNTS, BAG_FREQUENCIES = 0, 1  # ife_bag_values: what the dense bag stream delivers
 Z_STATE_BYTES = 32   # IFE_Z_STATE_BYTES: one state record of the slab Z pass, per line and job
 Z_OVERLAP_LO, Z_OVERLAP_HI = 3, 4  # IFE_Z_OVERLAP_*: neighbour planes around a slab's input
 NUM_FEATURES = 8
@@ -56,6 +57,7 @@ EXPORTS = (
     "ife_multi_emphysema_features_fetch", "ife_multi_emphysema_features_end",
     "ife_sort_f32", "ife_equalized_edges_f32", "ife_equalized_edges_f64", "ife_dense_histogram_f32", "ife_roi_histograms", "ife_bag_image",
     "ife_dense_rois", "ife_dense_roi_histograms", "ife_bag_image_dense",
+    "ife_bag_dense_stream_begin", "ife_bag_dense_stream_next", "ife_bag_dense_stream_end",
     "ife_samples_create", "ife_samples_destroy", "ife_samples_count", "ife_samples_clear",
     "ife_samples_add_features", "ife_samples_add_image", "ife_samples_sort",
     "ife_samples_equalized_edges", "ife_samples_read_column",
@@ -166,6 +168,11 @@ def load_library():
                                              i32, vp, i64, C.POINTER(i64), i32]
     lib.ife_bag_image_dense.argtypes = [vp, vp, i32, vp, i32, vp, i32, vd, C.POINTER(C.c_float), i32,
                                         C.POINTER(i64), vp, i32, vp, i64, C.POINTER(i64), i32]
+    lib.ife_bag_dense_stream_begin.argtypes = [vp, vp, i32, vp, i32, vp, i32, vd, C.POINTER(C.c_float), i32,
+                                               C.POINTER(i64), vp, i32, i32, i32, C.POINTER(i64),
+                                               C.POINTER(i64), i32]
+    lib.ife_bag_dense_stream_next.argtypes = [vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    lib.ife_bag_dense_stream_end.argtypes = [vp]
     lib.ife_samples_create.argtypes = [vp, i32, C.POINTER(vp)]
     lib.ife_samples_destroy.argtypes = [vp]
     lib.ife_samples_destroy.restype = None
@@ -719,6 +726,41 @@ class Context:
             _size_arg(size), edges.ctypes.data, ne, counts.ctypes.data, counts.shape[0],
             C.byref(got), MEM_HOST))
         return counts[:got.value]
+
+    def bag_image_dense_stream(self, image, mask, sigmas, size, edges, gen_mask=None,
+                               spacing=(1.0, 1.0, 1.0), values="frequencies", block_mb=0):
+        """The bag of bag_image_dense as a stream of row blocks: a generator of
+        (row0, ndarray[n_rows, n_sigmas*8, n_edges+1]), float32 frequencies (an empty histogram is
+        NaN) or uint32 counts (values="counts").  A block is a run of whole centre planes of at
+        most block_mb MiB (0: from the scratch budget); while one is copied the next is counted."""
+        if mask is None:
+            raise TypeError("a mask is required")
+        if values not in ("counts", "frequencies", BAG_COUNTS, BAG_FREQUENCIES):
+            raise ValueError("values must be 'counts' or 'frequencies'")
+        freq = values in ("frequencies", BAG_FREQUENCIES)
+        image, idt = _image_arg(image)
+        mask, mdt, mptr = _mask_arg(mask)
+        gen_mask, gdt, gptr = _mask_arg(gen_mask)
+        edges = np.ascontiguousarray(edges, np.float32)
+        ne = edges.shape[1]
+        d = _desc(image.shape, spacing)
+        sig = _sigma_arg(sigmas)
+        n, cap = C.c_int64(), C.c_int64()
+        self._chk(self._lib.ife_bag_dense_stream_begin(
+            self._h, image.ctypes.data, idt, mptr, mdt, gptr, gdt, C.byref(d), sig, len(sigmas),
+            _size_arg(size), edges.ctypes.data, ne, BAG_FREQUENCIES if freq else BAG_COUNTS,
+            int(block_mb), C.byref(n), C.byref(cap), MEM_HOST))
+        try:
+            while True:
+                rows = np.empty((max(cap.value, 1), 8 * len(sigmas), ne + 1), np.float32 if freq else np.uint32)
+                row0, got = C.c_int64(), C.c_int64()
+                self._chk(self._lib.ife_bag_dense_stream_next(self._h, rows.ctypes.data, rows.shape[0],
+                                                              C.byref(row0), C.byref(got)))
+                if got.value == 0:
+                    break
+                yield row0.value, rows[:got.value]
+        finally:
+            self._chk(self._lib.ife_bag_dense_stream_end(self._h))
 
     def samples(self, n_columns):
         return Samples(self, n_columns)

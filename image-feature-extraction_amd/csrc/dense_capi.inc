@@ -1,6 +1,7 @@
 // dense_capi.inc -- the dense bag entry points of include/ife_hip.h (ife_dense_rois,
-// ife_dense_roi_histograms, ife_bag_image_dense); included at the end of ife_capi.hip (shares its
-// context, staging and profiling helpers, and clamp01 / the scans of stats_capi.inc).
+// ife_dense_roi_histograms, ife_bag_image_dense, ife_bag_dense_stream_begin / _next / _end);
+// included at the end of ife_capi.hip (shares its context, staging and profiling helpers, and
+// clamp01 / the scans of stats_capi.inc).
 
 namespace {
 
@@ -41,16 +42,17 @@ struct DenseCentres {
   int64_t nseg, n;          // n: number of centres
 };
 
-// Flags and numbers the centres of `gen` (device) into ctx->dn_centres; blocks for the count.
-int dense_centres(ife_ctx *ctx, const void *dG, int gen_dtype, const DenseGeom &g, DenseCentres *out) {
+// Flags and numbers the centres of `gen` (device) into `buf` (ctx->dn_centres, or the stream's
+// own); blocks for the count.
+int dense_centres(ife_ctx *ctx, const void *dG, int gen_dtype, const DenseGeom &g, DevBuf &buf, DenseCentres *out) {
   const int64_t nseg = (int64_t)g.gx * g.ny * g.nz;
   const int64_t nchunks = (nseg + SCAN_CHUNK - 1) / SCAN_CHUNK;
   const size_t off_flag = (8 + (size_t)(nseg + nchunks) * 4 + 15) / 16 * 16;
-  int rc = ensure(ctx, ctx->dn_centres, off_flag + (size_t)g.nvox);
+  int rc = ensure(ctx, buf, off_flag + (size_t)g.nvox);
   if (rc) return rc;
-  unsigned long long *ctr = (unsigned long long *)ctx->dn_centres.p;
-  uint32_t *segs = (uint32_t *)((char *)ctx->dn_centres.p + 8), *sums = segs + nseg;
-  uint8_t *flag = (uint8_t *)ctx->dn_centres.p + off_flag;
+  unsigned long long *ctr = (unsigned long long *)buf.p;
+  uint32_t *segs = (uint32_t *)((char *)buf.p + 8), *sums = segs + nseg;
+  uint8_t *flag = (uint8_t *)buf.p + off_flag;
   {
     ProfScope ps(ctx, KK_DENSE_CODE);
     rc = with_mask_type(true, gen_dtype, dG, [&](auto gen) -> int {
@@ -87,6 +89,80 @@ int dense_budget(ife_ctx *ctx, size_t held, size_t *budget) {
   return IFE_OK;
 }
 
+// Components and bins the box passes take at a time: whole components (cg of them, all nb bins)
+// while they fit into `budget`, else one component and as many bins (bg) as fit.  Scratch per
+// group: nvox * cg * (code_bytes + 3 * bg) bytes (one byte after x and two after y per plane, and
+// code_bytes = 1 where the codes of the group live in the scratch too, 0 where they exist already).
+int dense_groups(ife_ctx *ctx, size_t budget, size_t nvox, int ncomp, int nb, int code_bytes, int *cg, int *bg) {
+  *cg = (int)std::min<size_t>({(size_t)ncomp, budget / (nvox * (code_bytes + 3 * (size_t)nb)), (size_t)1024});
+  *bg = nb;
+  if (*cg < 1) {
+    *cg = 1;
+    *bg = budget > code_bytes * nvox ? (int)std::min<size_t>((budget - code_bytes * nvox) / (3 * nvox), (size_t)nb) : 0;
+    if (*bg < 1)
+      return fail(ctx, IFE_E_NOMEM, "the dense box counts need %zu bytes of scratch for one bin, %zu are available",
+                  (3 + code_bytes) * nvox, budget);
+  }
+  return IFE_OK;
+}
+
+// Bin codes of components [c0, c0 + nc) of one feature volume (device): code[c - c0][voxel].
+int dense_code(ife_ctx *ctx, const float *dF, int64_t comp_stride, int64_t vox_stride, int c0, int nc, const void *dM,
+               int mask_dtype, int64_t nvox, const float *dEdges, int n_edges, uint8_t *code) {
+  ProfScope ps(ctx, KK_DENSE_CODE);
+  const dim3 grid((unsigned)std::min<int64_t>((nvox + 255) / 256, 1 << 16), (unsigned)nc);
+  return with_mask_type(true, mask_dtype, dM, [&](auto msk) -> int {
+    using TM = std::remove_cv_t<std::remove_pointer_t<decltype(msk)>>;
+    hipLaunchKernelGGL(dense_code_kernel<TM>, grid, dim3(256), 0, ctx->stream, dF, msk, dEdges, code, nvox,
+                       comp_stride, vox_stride, c0, n_edges);
+    IFE_HIP(ctx, hipGetLastError());
+    return IFE_OK;
+  });
+}
+
+// Where the z pass stores: counts[(number - row0) * row_stride + column * col_stride].
+struct DenseOut {
+  uint32_t *counts;
+  int64_t row0, row_stride, col_stride;
+};
+
+// The box passes over nc components whose codes are at code[c * code_stride + voxel of g], the nb
+// bins in groups of bg; the counts go to columns col0 + c * nb + bin of `out`.  g may be a block
+// of planes of a larger volume: code, flag and seg_base then point at the block's first plane.
+// scratch: ys [planes][g.nvox] two bytes, then xs [planes][g.nvox] one byte, planes >= nc * bg.
+int dense_box_passes(ife_ctx *ctx, const uint8_t *code, int64_t code_stride, int nc, const DenseGeom &g,
+                     const uint8_t *flag, const uint32_t *seg_base, void *scratch, size_t planes, int bg, int nb,
+                     const DenseOut &out, int64_t col0) {
+  uint16_t *ys = (uint16_t *)scratch;
+  uint8_t *xs = (uint8_t *)(ys + planes * (size_t)g.nvox);
+  // marching passes: a wave covers `chunk` outputs after a start-up of (window - 1) reads
+  const int64_t nyv = g.ny - g.sy + 1, nzv = g.nz - g.sz + 1;
+  const int ychunk = (int)std::min<int64_t>(std::max<int64_t>(2 * (int64_t)g.sy, 64), nyv);
+  const int zchunk = (int)std::min<int64_t>(std::max<int64_t>(2 * (int64_t)g.sz, 64), nzv);
+  const int nych = (int)((nyv + ychunk - 1) / ychunk), nzch = (int)((nzv + zchunk - 1) / zchunk);
+  for (int b0 = 0; b0 < nb; b0 += bg) {
+    const int nbins = std::min(bg, nb - b0);
+    const int64_t np = (int64_t)nc * nbins;
+    {
+      ProfScope ps(ctx, KK_DENSE_XY);
+      const int64_t wx = (int64_t)g.gx * g.ny * g.nz * nc, wy = (int64_t)g.gx * g.nz * nych * np;
+      hipLaunchKernelGGL(dense_box_x_kernel, dim3(dense_blocks(wx)), dim3(256), 0, ctx->stream, code, code_stride,
+                         xs, g, b0, nbins, wx);
+      hipLaunchKernelGGL(dense_box_y_kernel, dim3(dense_blocks(wy)), dim3(256), 0, ctx->stream, xs, ys, g, ychunk,
+                         nych, wy);
+    }
+    {
+      ProfScope ps(ctx, KK_DENSE_Z);
+      const int64_t wz = (int64_t)g.gx * nyv * nzch * np;
+      hipLaunchKernelGGL(dense_box_z_kernel, dim3(dense_blocks(wz)), dim3(256), 0, ctx->stream, ys, flag, seg_base,
+                         out.counts, g, nbins, nb, out.row0, out.row_stride, out.col_stride, col0 + b0, zchunk, nzch,
+                         wz);
+    }
+    IFE_HIP(ctx, hipGetLastError());
+  }
+  return IFE_OK;
+}
+
 // The box counts of components [0, ncomp) of one feature volume (device), written at the centres:
 // dCounts[number * row_words + col0 + c * (n_edges + 1) + bin].  dEdges: [ncomp][n_edges], device.
 // Scratch per group of cg components and bg bins: nvox * cg * (1 + 3 * bg) bytes (codes; one byte
@@ -96,68 +172,28 @@ int dense_count(ife_ctx *ctx, const float *dF, int layout, int ncomp, const void
                 int64_t row_words, int64_t col0, size_t budget) {
   const int nb = n_edges + 1;
   const size_t nvox = (size_t)g.nvox;
-  // whole components while they fit, else one component and as many bins as fit
-  int cg = (int)std::min<size_t>({(size_t)ncomp, budget / (nvox * (1 + 3 * (size_t)nb)), (size_t)1024});
-  int bg = nb;
-  if (cg < 1) {
-    cg = 1;
-    bg = budget > nvox ? (int)std::min<size_t>((budget - nvox) / (3 * nvox), (size_t)nb) : 0;
-    if (bg < 1)
-      return fail(ctx, IFE_E_NOMEM, "the dense box counts need %zu bytes of scratch for one bin, %zu are available",
-                  4 * nvox, budget);
-  }
-  const size_t planes = (size_t)cg * bg;
-  int rc = ensure(ctx, ctx->dn_ws, nvox * (3 * planes + cg));
+  int cg, bg;
+  int rc = dense_groups(ctx, budget, nvox, ncomp, nb, 1, &cg, &bg);
   if (rc) return rc;
-  uint16_t *ys = (uint16_t *)ctx->dn_ws.p;  // [planes][nvox], then xs [planes][nvox], then codes [cg][nvox]
-  uint8_t *xs = (uint8_t *)(ys + planes * nvox), *code = xs + planes * nvox;
+  const size_t planes = (size_t)cg * bg;
+  if ((rc = ensure(ctx, ctx->dn_ws, nvox * (3 * planes + cg)))) return rc;
+  uint8_t *code = (uint8_t *)ctx->dn_ws.p + 3 * planes * nvox;  // behind ys and xs: [cg][nvox]
   const int64_t comp_stride = layout == IFE_PLANAR ? g.nvox : 1, vox_stride = layout == IFE_PLANAR ? 1 : ncomp;
-  // marching passes: a wave covers `chunk` outputs after a start-up of (window - 1) reads
-  const int64_t nyv = g.ny - g.sy + 1, nzv = g.nz - g.sz + 1;
-  const int ychunk = (int)std::min<int64_t>(std::max<int64_t>(2 * (int64_t)g.sy, 64), nyv);
-  const int zchunk = (int)std::min<int64_t>(std::max<int64_t>(2 * (int64_t)g.sz, 64), nzv);
-  const int nych = (int)((nyv + ychunk - 1) / ychunk), nzch = (int)((nzv + zchunk - 1) / zchunk);
+  const DenseOut out = {dCounts, 0, row_words, 1};
   for (int c0 = 0; c0 < ncomp; c0 += cg) {
     const int nc = std::min(cg, ncomp - c0);
-    {
-      ProfScope ps(ctx, KK_DENSE_CODE);
-      const dim3 grid((unsigned)std::min<int64_t>((g.nvox + 255) / 256, 1 << 16), (unsigned)nc);
-      rc = with_mask_type(true, mask_dtype, dM, [&](auto msk) -> int {
-        using TM = std::remove_cv_t<std::remove_pointer_t<decltype(msk)>>;
-        hipLaunchKernelGGL(dense_code_kernel<TM>, grid, dim3(256), 0, ctx->stream, dF, msk, dEdges, code, g.nvox,
-                           comp_stride, vox_stride, c0, n_edges);
-        IFE_HIP(ctx, hipGetLastError());
-        return IFE_OK;
-      });
-      if (rc) return rc;
-    }
-    for (int b0 = 0; b0 < nb; b0 += bg) {
-      const int nbins = std::min(bg, nb - b0);
-      const int64_t np = (int64_t)nc * nbins;
-      {
-        ProfScope ps(ctx, KK_DENSE_XY);
-        const int64_t wx = (int64_t)g.gx * g.ny * g.nz * nc, wy = (int64_t)g.gx * g.nz * nych * np;
-        hipLaunchKernelGGL(dense_box_x_kernel, dim3(dense_blocks(wx)), dim3(256), 0, ctx->stream, code, xs, g, b0,
-                           nbins, wx);
-        hipLaunchKernelGGL(dense_box_y_kernel, dim3(dense_blocks(wy)), dim3(256), 0, ctx->stream, xs, ys, g, ychunk,
-                           nych, wy);
-      }
-      {
-        ProfScope ps(ctx, KK_DENSE_Z);
-        const int64_t wz = (int64_t)g.gx * nyv * nzch * np;
-        hipLaunchKernelGGL(dense_box_z_kernel, dim3(dense_blocks(wz)), dim3(256), 0, ctx->stream, ys, cen.flag,
-                           cen.seg_base, dCounts, g, nbins, nb, row_words, col0 + (int64_t)c0 * nb + b0, zchunk, nzch,
-                           wz);
-      }
-      IFE_HIP(ctx, hipGetLastError());
-    }
+    if ((rc = dense_code(ctx, dF, comp_stride, vox_stride, c0, nc, dM, mask_dtype, g.nvox, dEdges, n_edges, code)))
+      return rc;
+    if ((rc = dense_box_passes(ctx, code, g.nvox, nc, g, cen.flag, cen.seg_base, ctx->dn_ws.p, planes, bg, nb, out,
+                               col0 + (int64_t)c0 * nb)))
+      return rc;
   }
   return IFE_OK;
 }
 
 // Arguments shared by the two histogram calls (everything but their inputs).
 int dense_hist_check(ife_ctx *ctx, const void *mask, int mask_dtype, const void *gen_mask, int gen_mask_dtype,
-                     const float *edges, int n_edges, const uint32_t *counts, int64_t capacity,
+                     const float *edges, int n_edges, const void *counts, int64_t capacity,
                      const int64_t *n_rois, int mem) {
   int rc = check_mem(ctx, mem);
   if (rc) return rc;
@@ -204,7 +240,7 @@ int ife_dense_rois(ife_ctx *ctx, const void *gen_mask, int gen_mask_dtype, const
   const void *dG;
   if ((rc = stage_in(ctx, mem, gen_mask, (size_t)g.nvox * dtype_size(gen_mask_dtype), ctx->st_mask, &dG))) return rc;
   DenseCentres cen;
-  if ((rc = dense_centres(ctx, dG, gen_mask_dtype, g, &cen))) return rc;
+  if ((rc = dense_centres(ctx, dG, gen_mask_dtype, g, ctx->dn_centres, &cen))) return rc;
   *n_rois = cen.n;
   if (!rois || cen.n == 0) return IFE_OK;
   if (cen.n > capacity) return dense_too_many(ctx, cen.n, capacity);
@@ -259,7 +295,7 @@ int ife_dense_roi_histograms(ife_ctx *ctx, const float *features, int layout, in
     dG = gen_mask;
   }
   DenseCentres cen;
-  if ((rc = dense_centres(ctx, dG ? dG : dM, dG ? gen_mask_dtype : mask_dtype, g, &cen))) return rc;
+  if ((rc = dense_centres(ctx, dG ? dG : dM, dG ? gen_mask_dtype : mask_dtype, g, ctx->dn_centres, &cen))) return rc;
   *n_rois = cen.n;
   if (cen.n > capacity) return dense_too_many(ctx, cen.n, capacity);
   if (cen.n == 0) return IFE_OK;
@@ -311,7 +347,7 @@ int ife_bag_image_dense(ife_ctx *ctx, const void *image, int image_dtype, const 
   const float *dE = (const float *)((char *)ctx->st_aux.p + off_e);
   IFE_HIP(ctx, hipMemcpyAsync((char *)ctx->st_aux.p + off_e, edges, ebytes, hipMemcpyHostToDevice, ctx->stream));
   DenseCentres cen;
-  if ((rc = dense_centres(ctx, dG ? dG : dM, dG ? gen_mask_dtype : mask_dtype, g, &cen))) return rc;
+  if ((rc = dense_centres(ctx, dG ? dG : dM, dG ? gen_mask_dtype : mask_dtype, g, ctx->dn_centres, &cen))) return rc;
   *n_rois = cen.n;
   if (cen.n > capacity) return dense_too_many(ctx, cen.n, capacity);
   if (cen.n == 0) return IFE_OK;
@@ -343,6 +379,247 @@ int ife_bag_image_dense(ife_ctx *ctx, const void *image, int image_dtype, const 
   }
   IFE_HIP(ctx, hipMemcpyAsync(counts, ctx->st_out.p, cbytes, hipMemcpyDeviceToHost, ctx->stream));
   IFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return IFE_OK;
+}
+
+}  // extern "C"
+
+// ---- the dense bag as a stream of row blocks --------------------------------------------------------
+// The bin codes of all scales stay on the device (one byte per voxel and column); the regions of a
+// block of centre planes (dense_plan.hpp) are counted from them into a planar block buffer,
+// turned into row-major counts or frequencies (dense_freq_kernel) and copied out on a copy stream
+// while the next block is counted.  Nothing as large as the bag exists anywhere.
+namespace {
+
+void dense_stream_release(ife_ctx *ctx) {
+  auto &ds = ctx->ds;
+  if (ds.open) {  // kernels or a copy of a block may still be in flight
+    (void)hipStreamSynchronize(ctx->stream);
+    if (ds.copy) (void)hipStreamSynchronize(ds.copy);
+  }
+  for (DevBuf *b : {&ds.codes, &ds.centres, &ds.ws, &ds.planar, &ds.rows[0], &ds.rows[1]})
+    if (b->p) {
+      (void)hipFree(b->p);
+      b->p = nullptr;
+      b->cap = 0;
+    }
+  for (auto &e : ds.done)
+    if (e) {
+      (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+  ds.blocks.clear();
+  ds.next = ds.counted = 0;
+  ds.n_rois = 0;
+  ds.open = false;
+}
+
+// Enqueues block k: the box passes from the codes of its planes into the planar buffer, then the
+// row-major block into rows[k % 2], and the event that says so.  Does not wait.
+int dense_stream_count(ife_ctx *ctx, size_t k) {
+  auto &ds = ctx->ds;
+  const DenseBlock &b = ds.blocks[k];
+  const DenseGeom &g = ds.g;
+  const int64_t plane = g.nx * g.ny, z0 = b.zc0 - g.hz;  // z0: first plane of codes the block reads
+  DenseGeom gb = g;
+  gb.nz = b.zc1 - b.zc0 + g.sz - 1;
+  gb.nvox = plane * gb.nz;
+  const DenseOut out = {(uint32_t *)ds.planar.p, b.row0, 1, ds.ld};
+  int rc;
+  for (int c0 = 0; c0 < ds.ncol; c0 += ds.cg) {
+    const int nc = std::min(ds.cg, ds.ncol - c0);
+    if ((rc = dense_box_passes(ctx, (const uint8_t *)ds.codes.p + (size_t)c0 * g.nvox + z0 * plane, g.nvox, nc, gb,
+                               ds.flag + z0 * plane, ds.seg_base + (int64_t)g.gx * g.ny * z0, ds.ws.p,
+                               (size_t)ds.cg * ds.bg, ds.bg, ds.nb, out, (int64_t)c0 * ds.nb)))
+      return rc;
+  }
+  {
+    ProfScope ps(ctx, KK_DENSE_Z);  // the kernel-time table is full: the transposition counts as the z pass's store
+    // rows x whole histograms per tile: 64 rows while one histogram fits beside them, else 32
+    const int tr_log2 = ds.nb * 65 <= DENSE_FREQ_LDS_WORDS ? 6 : 5, tr = 1 << tr_log2;
+    const int hists = std::max(1, std::min(ds.ncol, DENSE_FREQ_LDS_WORDS / (tr + 1) / ds.nb));
+    const dim3 grid((unsigned)((b.n_rows + tr - 1) / tr), (unsigned)std::min((ds.ncol + hists - 1) / hists, 65535));
+    if (ds.values == IFE_BAG_FREQUENCIES)
+      hipLaunchKernelGGL(dense_freq_kernel<true>, grid, dim3(256), 0, ctx->stream, (const uint32_t *)ds.planar.p,
+                         (uint32_t *)ds.rows[k % 2].p, b.n_rows, ds.ld, ds.ncol, ds.nb, hists, tr_log2);
+    else
+      hipLaunchKernelGGL(dense_freq_kernel<false>, grid, dim3(256), 0, ctx->stream, (const uint32_t *)ds.planar.p,
+                         (uint32_t *)ds.rows[k % 2].p, b.n_rows, ds.ld, ds.ncol, ds.nb, hists, tr_log2);
+    IFE_HIP(ctx, hipGetLastError());
+  }
+  IFE_HIP(ctx, hipEventRecord(ds.done[k % 2], ctx->stream));
+  ds.counted = k + 1;
+  return IFE_OK;
+}
+
+int dense_stream_begin(ife_ctx *ctx, const void *image, int image_dtype, const void *mask, int mask_dtype,
+                       const void *gen_mask, int gen_mask_dtype, const ife_volume_desc *vol, const float *sigmas,
+                       int n_sigmas, const DenseGeom &g, const float *edges, int n_edges, int block_mb,
+                       int64_t *max_block_rows, int mem) {
+  auto &ds = ctx->ds;
+  int rc;
+  const size_t nvox = (size_t)g.nvox, gbytes = gen_mask ? nvox * dtype_size(gen_mask_dtype) : 0;
+  const int ncol = n_sigmas * IFE_NUM_FEATURES, nb = n_edges + 1;
+  const size_t ebytes = (size_t)ncol * n_edges * 4, off_e = (gbytes + 15) / 16 * 16;
+  // 1. uploads (all of them before the count of the centres comes back, which waits for them: the
+  // caller may reuse its host arrays once _begin returns)
+  const void *dI, *dM, *dG = gen_mask;
+  if ((rc = stage_in(ctx, mem, mask, nvox * dtype_size(mask_dtype), ctx->st_mask, &dM))) return rc;
+  if ((rc = ensure(ctx, ctx->st_aux, off_e + ebytes))) return rc;  // generating mask (HOST mode), edges
+  if (gen_mask && mem == IFE_MEM_HOST) {
+    IFE_HIP(ctx, hipMemcpyAsync(ctx->st_aux.p, gen_mask, gbytes, hipMemcpyHostToDevice, ctx->stream));
+    dG = ctx->st_aux.p;
+  }
+  const float *dE = (const float *)((char *)ctx->st_aux.p + off_e);
+  IFE_HIP(ctx, hipMemcpyAsync((char *)ctx->st_aux.p + off_e, edges, ebytes, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = stage_in(ctx, mem, image, nvox * dtype_size(image_dtype), ctx->st_img, &dI))) return rc;
+  // 3. the centres, and per centre plane the number of its first region
+  DenseCentres cen;
+  if ((rc = dense_centres(ctx, dG ? dG : dM, dG ? gen_mask_dtype : mask_dtype, g, ds.centres, &cen))) return rc;
+  ds.n_rois = cen.n;
+  if (cen.n == 0) return IFE_OK;
+  const int64_t nplanes = g.nz - g.sz + 1;
+  std::vector<uint32_t> first((size_t)nplanes);
+  if ((rc = ensure(ctx, ctx->st_out, (size_t)nplanes * 4))) return rc;
+  {
+    ProfScope ps(ctx, KK_DENSE_CODE);
+    hipLaunchKernelGGL(dense_plane_first_kernel, dim3((unsigned)((nplanes + 255) / 256)), dim3(256), 0, ctx->stream,
+                       cen.seg_base, (uint32_t *)ctx->st_out.p, (int64_t)g.gx * g.ny, (int64_t)g.hz, nplanes);
+    IFE_HIP(ctx, hipGetLastError());
+  }
+  IFE_HIP(ctx, hipMemcpyAsync(first.data(), ctx->st_out.p, (size_t)nplanes * 4, hipMemcpyDeviceToHost, ctx->stream));
+  IFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<int64_t> plane_rows((size_t)nplanes);
+  for (int64_t o = 0; o < nplanes; ++o)
+    plane_rows[(size_t)o] = (o + 1 < nplanes ? (int64_t)first[(size_t)o + 1] : cen.n) - (int64_t)first[(size_t)o];
+  // the budget: features of a group of scales (at most half, as in ife_bag_image_dense), the codes,
+  // and of the rest an eighth per block buffer (three of them) and half for the box passes
+  size_t budget;
+  if ((rc = dense_budget(ctx, ctx->dn_feat.cap, &budget))) return rc;
+  const size_t scale_bytes = nvox * IFE_NUM_FEATURES * 4, off_f = (nvox + 15) / 16 * 16;
+  const int sg = (int)std::min<size_t>(std::max<size_t>(budget / 2 / scale_bytes, 1), (size_t)n_sigmas);
+  const size_t fbytes = off_f + (size_t)sg * scale_bytes, cbytes = (size_t)ncol * nvox;
+  const size_t rest = budget > fbytes + cbytes ? budget - fbytes - cbytes : 0;
+  const size_t row_bytes = (size_t)ncol * nb * 4;
+  ds.blocks = dense_plan(plane_rows, row_bytes, block_mb > 0 ? (size_t)block_mb << 20 : rest / 8, g.sz);
+  int64_t max_rows = 0, max_planes = 0;
+  for (const DenseBlock &b : ds.blocks) {
+    max_rows = std::max(max_rows, b.n_rows);
+    max_planes = std::max(max_planes, b.zc1 - b.zc0 + g.sz - 1);
+  }
+  const size_t bvox = (size_t)(g.nx * g.ny * max_planes);
+  if ((rc = dense_groups(ctx, rest / 2, bvox, ncol, nb, 0, &ds.cg, &ds.bg))) return rc;
+  ds.g = g;
+  ds.flag = cen.flag;
+  ds.seg_base = cen.seg_base;
+  ds.ncol = ncol;
+  ds.nb = nb;
+  ds.ld = (max_rows + 63) / 64 * 64;
+  if ((rc = ensure(ctx, ctx->dn_feat, fbytes))) return rc;
+  if ((rc = ensure(ctx, ds.codes, cbytes))) return rc;
+  if ((rc = ensure(ctx, ds.ws, bvox * 3 * ds.cg * ds.bg))) return rc;
+  if ((rc = ensure(ctx, ds.planar, (size_t)ds.ld * row_bytes))) return rc;
+  for (size_t i = 0; i < std::min<size_t>(ds.blocks.size(), 2); ++i) {
+    if ((rc = ensure(ctx, ds.rows[i], (size_t)max_rows * row_bytes))) return rc;
+    IFE_HIP(ctx, hipEventCreateWithFlags(&ds.done[i], hipEventDisableTiming));
+  }
+  if (!ds.copy) IFE_HIP(ctx, hipStreamCreateWithFlags(&ds.copy, hipStreamNonBlocking));
+  // 2., 4., 5. clamped labels, the features of a group of scales, their codes; the features go
+  uint8_t *clamp = (uint8_t *)ctx->dn_feat.p;
+  float *feat = (float *)((char *)ctx->dn_feat.p + off_f);
+  if ((rc = launch_clamp01(ctx, dM, mask_dtype, clamp, g.nvox))) return rc;
+  for (int s0 = 0; s0 < n_sigmas; s0 += sg) {
+    const int ns = std::min(sg, n_sigmas - s0);
+    if ((rc = ife_emphysema_features(ctx, dI, image_dtype, clamp, IFE_U8, vol, sigmas + s0, ns, feat, IFE_PLANAR,
+                                     IFE_MEM_DEVICE)))
+      return rc;
+    for (int i = 0; i < ns; ++i)
+      if ((rc = dense_code(ctx, feat + (size_t)i * nvox * IFE_NUM_FEATURES, g.nvox, 1, 0, IFE_NUM_FEATURES, clamp,
+                           IFE_U8, g.nvox, dE + (size_t)(s0 + i) * IFE_NUM_FEATURES * n_edges, n_edges,
+                           (uint8_t *)ds.codes.p + (size_t)(s0 + i) * IFE_NUM_FEATURES * nvox)))
+        return rc;
+  }
+  *max_block_rows = max_rows;
+  return dense_stream_count(ctx, 0);  // the first block is under way when _begin returns
+}
+
+}  // namespace
+
+extern "C" {
+
+int ife_bag_dense_stream_begin(ife_ctx *ctx, const void *image, int image_dtype, const void *mask, int mask_dtype,
+                               const void *gen_mask, int gen_mask_dtype, const ife_volume_desc *vol,
+                               const float *sigmas, int n_sigmas, const int64_t size[3], const float *edges,
+                               int n_edges, int values, int block_mb, int64_t *n_rois, int64_t *max_block_rows,
+                               int mem) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_vol(ctx, vol, true))) return rc;
+  if (!image || !sigmas) return fail(ctx, IFE_E_ARG, "null pointer");
+  // max_block_rows stands where the bag calls have their output array: it must not be null either
+  if ((rc = dense_hist_check(ctx, mask, mask_dtype, gen_mask, gen_mask_dtype, edges, n_edges, max_block_rows, 0,
+                             n_rois, mem)))
+    return rc;
+  if ((rc = check_sigmas(ctx, sigmas, n_sigmas))) return rc;
+  if ((rc = check_image_dtype(ctx, image_dtype))) return rc;
+  if (values != IFE_BAG_COUNTS && values != IFE_BAG_FREQUENCIES)
+    return fail(ctx, IFE_E_ARG, "values must be IFE_BAG_COUNTS or IFE_BAG_FREQUENCIES");
+  if (block_mb < 0) return fail(ctx, IFE_E_ARG, "the block bound must be >= 0 MiB");
+  DenseGeom g;
+  bool empty = false;
+  if ((rc = dense_geom(ctx, vol, size, true, &g, &empty))) return rc;
+  dense_stream_release(ctx);  // drop an earlier, unfinished stream
+  *n_rois = 0;
+  *max_block_rows = 0;
+  ctx->ds.values = values;
+  ctx->ds.open = true;  // zero regions is a stream too: its first _next reports the end
+  if (empty) return IFE_OK;
+  rc = dense_stream_begin(ctx, image, image_dtype, mask, mask_dtype, gen_mask, gen_mask_dtype, vol, sigmas, n_sigmas,
+                          g, edges, n_edges, block_mb, max_block_rows, mem);
+  if (rc) {
+    dense_stream_release(ctx);
+    return rc;
+  }
+  *n_rois = ctx->ds.n_rois;
+  return IFE_OK;
+}
+
+int ife_bag_dense_stream_next(ife_ctx *ctx, void *rows, int64_t capacity_rows, int64_t *row0, int64_t *n_rows) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!row0 || !n_rows) return fail(ctx, IFE_E_ARG, "null pointer");
+  auto &ds = ctx->ds;
+  if (!ds.open) return fail(ctx, IFE_E_STATE, "no dense stream is open (ife_bag_dense_stream_begin starts one)");
+  if (ds.next == ds.blocks.size()) {
+    *row0 = ds.n_rois;
+    *n_rows = 0;
+    return IFE_OK;
+  }
+  const size_t k = ds.next;
+  const DenseBlock &b = ds.blocks[k];
+  *row0 = b.row0;
+  *n_rows = b.n_rows;
+  if (capacity_rows < b.n_rows)
+    return fail(ctx, IFE_E_SIZE, "the block has %lld rows, the array holds %lld", (long long)b.n_rows,
+                (long long)capacity_rows);
+  if (!rows) return fail(ctx, IFE_E_ARG, "null pointer");
+  if (ds.counted <= k && (rc = dense_stream_count(ctx, k))) return rc;
+  // the next block is counted (into the other buffer) while this one is copied; the copy of the
+  // block before it out of that buffer has finished, the _next that delivered it waited for it
+  if (k + 1 < ds.blocks.size() && ds.counted <= k + 1 && (rc = dense_stream_count(ctx, k + 1))) return rc;
+  IFE_HIP(ctx, hipStreamWaitEvent(ds.copy, ds.done[k % 2], 0));
+  IFE_HIP(ctx, hipMemcpyAsync(rows, ds.rows[k % 2].p, (size_t)b.n_rows * ds.ncol * ds.nb * 4, hipMemcpyDeviceToHost,
+                              ds.copy));
+  IFE_HIP(ctx, hipStreamSynchronize(ds.copy));
+  ds.next = k + 1;
+  return IFE_OK;
+}
+
+int ife_bag_dense_stream_end(ife_ctx *ctx) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!ctx->ds.open) return fail(ctx, IFE_E_STATE, "no dense stream is open");
+  dense_stream_release(ctx);
   return IFE_OK;
 }
 

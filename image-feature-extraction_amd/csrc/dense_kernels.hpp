@@ -15,7 +15,14 @@
 //   y pass   lanes along x, marching y: running sum (add the row that enters, subtract the one
 //            that leaves), one byte in, two bytes out
 //   z pass   the same along z, two bytes in; stores nothing but the final counts, at the centres,
-//            straight into counts[row][component][bin]
+//            straight into counts[row][component][bin] (or, for the stream of row blocks, into a
+//            planar block buffer [column][row in block], so that a wave's stores are one run)
+//   freq     stream only: the planar block to the row-major block that goes to the host,
+//            transposed through LDS, as counts or as DenseHistogram::getFrequencies forms them
+//
+// The x and y passes work plane by plane, so a block of centre planes [zc0, zc1) runs them on a
+// DenseGeom whose nz is the block's plane count (zc1 - zc0 + sz - 1) with pointers offset to plane
+// zc0 - hz; the z pass takes the flags and segment bases offset likewise and the block's first row.
 //
 // Work per voxel, component and bin is constant: it does not grow with the box.  Everything is
 // integer counting and every output word has exactly one writer, so the result does not depend on
@@ -130,10 +137,11 @@ __global__ __launch_bounds__(256) void dense_code_kernel(const float *__restrict
 // voxels of the window [x - hx, x - hx + sx) of i's row with code == b0 + b; 0 where the window
 // leaves the row.  One wave per (row segment, component): the codes of the segment and of the
 // pieces the windows reach into are read once, per bin a ballot per piece and a popcount of the
-// window's bits in it.  nwork = gx * ny * nz * ncomp.
+// window's bits in it.  nwork = gx * ny * nz * ncomp.  code_stride: bytes from one component's
+// codes to the next (g.nvox, or the whole volume's where g is a block of its planes).
 __global__ __launch_bounds__(256) void dense_box_x_kernel(const uint8_t *__restrict__ code,
-                                                          uint8_t *__restrict__ xs, DenseGeom g, int b0,
-                                                          int nbins, int64_t nwork) {
+                                                          int64_t code_stride, uint8_t *__restrict__ xs,
+                                                          DenseGeom g, int b0, int nbins, int64_t nwork) {
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -151,7 +159,7 @@ __global__ __launch_bounds__(256) void dense_box_x_kernel(const uint8_t *__restr
   for (int64_t w = wave0; w < nwork; w += nwaves) {
     const int64_t seg = w % g.gx, t = w / g.gx, row = t % nrows, c = t / nrows;
     const int64_t x = seg * 64 + lane, p0 = seg * 64 - g.hx;
-    const uint8_t *src = code + c * g.nvox + row * g.nx;
+    const uint8_t *src = code + c * code_stride + row * g.nx;
     int k[DENSE_X_PIECES];
 #pragma unroll
     for (int j = 0; j < DENSE_X_PIECES; ++j) {
@@ -204,14 +212,17 @@ __global__ __launch_bounds__(256) void dense_box_y_kernel(const uint8_t *__restr
 
 // z pass of plane p = c * nbins + b: the running sum of ys[p] along z is the count of bin b0 + b
 // of component c in the box around (x, y, z); it is stored only where flag says centre, at
-// counts[number * row_words + col0 + c * nb + b].  Lanes along x, a wave marches `chunk` planes of
-// one (segment, y, plane) for the ny - sy + 1 rows y whose window fits.
+// counts[(number - row0) * row_stride + (col0 + c * nb + b) * col_stride]: row-major rows with
+// (row_words, 1), a planar block [column][row in block] with (1, rows the block buffer holds).
+// row0: the number of the first region of g (0 for a whole volume).  Lanes along x, a wave marches
+// `chunk` planes of one (segment, y, plane) for the ny - sy + 1 rows y whose window fits.
 // nwork = gx * (ny - sy + 1) * nchunks * nplanes.
 __global__ __launch_bounds__(256) void dense_box_z_kernel(const uint16_t *__restrict__ ys,
                                                           const uint8_t *__restrict__ flag,
                                                           const uint32_t *__restrict__ seg_base,
                                                           uint32_t *__restrict__ counts, DenseGeom g,
-                                                          int nbins, int nb, int64_t row_words,
+                                                          int nbins, int nb, int64_t row0,
+                                                          int64_t row_stride, int64_t col_stride,
                                                           int64_t col0, int chunk, int nchunks,
                                                           int64_t nwork) {
   const int lane = threadIdx.x & 63;
@@ -237,11 +248,72 @@ __global__ __launch_bounds__(256) void dense_box_z_kernel(const uint16_t *__rest
       const bool on = live && flag[zc * plane + at] != 0;
       const uint64_t m = __builtin_amdgcn_ballot_w64(on);
       if (on) {
-        const int64_t number = (int64_t)seg_base[seg + g.gx * (y + g.ny * zc)] + lanes_below(m);
-        counts[number * row_words + col] = s;
+        const int64_t number = (int64_t)seg_base[seg + g.gx * (y + g.ny * zc)] + lanes_below(m) - row0;
+        counts[number * row_stride + col * col_stride] = s;
       }
       s -= in[o * plane];
     }
+  }
+}
+
+// first[o] = number of the first region of centre plane hz + o (seg_base of the plane's first
+// segment), for the block plan on the host.
+__global__ __launch_bounds__(256) void dense_plane_first_kernel(const uint32_t *__restrict__ seg_base,
+                                                                uint32_t *__restrict__ first, int64_t plane_segs,
+                                                                int64_t hz, int64_t nplanes) {
+  const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o < nplanes) first[o] = seg_base[(hz + o) * plane_segs];
+}
+
+// The planar block planar[column][row in block] (ld words per column) to the row-major block
+// rows[row in block][nhist][nb] that goes to the host.  FREQ: every histogram as
+// DenseHistogram::getFrequencies forms it (DenseHistogram.h:55-60): the nb counts summed into an
+// int, then (float)count / (float)sum, NaN throughout for an empty histogram; else the counts.
+//
+// A workgroup stages a tile of 2^tr_log2 rows x `hists` whole histograms in LDS, a column of the
+// tile at pitch rows + 1 words.  In: lanes along the rows of one column, contiguous in global
+// memory and in LDS.  Sums: a thread per (row, histogram), lanes along rows, LDS addresses
+// consecutive; the quotients replace the counts in place.  Out: lanes along the words of an output
+// row (and on into the next row of the tile: one run when the tile spans the row), LDS addresses
+// pitch words apart -- the pitch is odd, so the 32 lanes of a half wave fall on 32 different banks.
+// Nothing is assumed to divide: the last tile of rows and the last group of histograms are partial.
+// Grid: x = row tiles, y = histogram groups (strided when there are more than the grid holds).
+constexpr int DENSE_FREQ_LDS_WORDS = 12288;  // 48 KiB
+template <bool FREQ>
+__global__ __launch_bounds__(256) void dense_freq_kernel(const uint32_t *__restrict__ planar,
+                                                         uint32_t *__restrict__ rows, int64_t n_rows,
+                                                         int64_t ld, int nhist, int nb, int hists,
+                                                         int tr_log2) {
+  __shared__ uint32_t tile[DENSE_FREQ_LDS_WORDS];
+  const int tr = 1 << tr_log2, pitch = tr + 1;
+  const int64_t r0 = (int64_t)blockIdx.x * tr, row_words = (int64_t)nhist * nb;
+  const int nr = (int)min((int64_t)tr, n_rows - r0);
+  for (int h0 = blockIdx.y * hists; h0 < nhist; h0 += gridDim.y * hists) {
+    const int nh = min(hists, nhist - h0), wt = nh * nb;
+    const int64_t w0 = (int64_t)h0 * nb;
+    for (int i = threadIdx.x; i < wt << tr_log2; i += blockDim.x) {
+      const int c = i >> tr_log2, r = i & (tr - 1);
+      if (r < nr) tile[c * pitch + r] = planar[(w0 + c) * ld + r0 + r];
+    }
+    __syncthreads();
+    if (FREQ) {
+      for (int i = threadIdx.x; i < nh << tr_log2; i += blockDim.x) {
+        const int h = i >> tr_log2, r = i & (tr - 1);
+        if (r < nr) {
+          uint32_t *t = tile + h * nb * pitch + r;
+          uint32_t sum = 0;
+          for (int b = 0; b < nb; ++b) sum += t[b * pitch];
+          const float d = (float)(int)sum;
+          for (int b = 0; b < nb; ++b) t[b * pitch] = __float_as_uint((float)t[b * pitch] / d);
+        }
+      }
+      __syncthreads();
+    }
+    for (int i = threadIdx.x; i < nr * wt; i += blockDim.x) {
+      const int r = i / wt, j = i - r * wt;
+      rows[(r0 + r) * row_words + w0 + j] = tile[j * pitch + r];
+    }
+    __syncthreads();
   }
 }
 

@@ -24,6 +24,7 @@
 #include "stats_kernels.hpp"
 #include "distance_kernels.hpp"
 #include "dense_kernels.hpp"
+#include "dense_plan.hpp"
 #define IFE_IIR_NS iir_exact
 #define IFE_IIR_FMA 0
 #include "iir_kernels.inc"
@@ -147,6 +148,25 @@ struct ife_ctx {
   // dense bag: centre flags and numbers, the scratch of the box passes, clamped labels and features
   DevBuf dn_centres, dn_ws, dn_feat;
   int dense_scratch_mb = 0;  // IFE_OPT_DENSE_SCRATCH_MB: 0 = sized from the free device memory
+  // dense bag as a stream of row blocks (ife_bag_dense_stream_*, dense_capi.inc): everything the
+  // stream needs between calls is its own, so other calls on the context do not disturb it
+  struct DenseStream {
+    bool open = false;
+    DevBuf codes;    // [ncol][nvox] bin codes of every (scale, feature)
+    DevBuf centres;  // centre flags and segment bases (dense_centres)
+    DevBuf ws;       // scratch of the box passes of one block
+    DevBuf planar;   // the block the z pass fills: [ncol * nb][ld]
+    DevBuf rows[2];  // row-major blocks on their way to the host, block k in rows[k % 2]
+    hipEvent_t done[2] = {nullptr, nullptr};  // rows[i] is complete
+    hipStream_t copy = nullptr;               // device-to-host copies beside the counting of the next block
+    std::vector<DenseBlock> blocks;
+    size_t next = 0, counted = 0;  // next block to deliver; blocks whose counting is enqueued
+    DenseGeom g;
+    const uint8_t *flag = nullptr;
+    const uint32_t *seg_base = nullptr;
+    int ncol = 0, nb = 0, values = 0, cg = 0, bg = 0;
+    int64_t n_rois = 0, ld = 0;
+  } ds;
   DevBuf dj_ws;  // differential convolution: the field slots of one scale (diff_capi.inc)
   // streaming form of the scale loop (ife_emphysema_features_begin / _fetch / _end)
   DevBuf sc_out;                     // all scales, device resident
@@ -161,6 +181,8 @@ struct ife_ctx {
 };
 
 namespace {
+
+void dense_stream_release(ife_ctx *ctx);  // dense_capi.inc
 
 int fail(ife_ctx *ctx, int code, const char *fmt, ...) {
   char buf[512];
@@ -1090,6 +1112,8 @@ void ife_ctx_destroy(ife_ctx *ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   for (auto e : ctx->sc_done) (void)hipEventDestroy(e);
   if (ctx->sc_copy) (void)hipStreamDestroy(ctx->sc_copy);
+  dense_stream_release(ctx);
+  if (ctx->ds.copy) (void)hipStreamDestroy(ctx->ds.copy);
   std::vector<DevBuf *> bufs = {&ctx->pre[0], &ctx->pre[1], &ctx->st_img, &ctx->st_mask,
                                 &ctx->st_aux, &ctx->st_out, &ctx->sc_out, &ctx->edt_g,
                                 &ctx->edt_i, &ctx->edt_d2, &ctx->edt_part, &ctx->dn_centres,

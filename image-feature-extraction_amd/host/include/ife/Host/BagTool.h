@@ -9,9 +9,11 @@
 //
 // The features of all scales stay in HBM and the per-region histograms are counted there
 // (ife_bag_image; ife_roi_histograms on the image for the intensity variant; for the dense
-// variant ife_bag_image_dense, which takes the generator's rule in place of the box list and
-// counts by sliding box sums); only the counts come back.  Frequencies are formed as
-// DenseHistogram::getFrequencies does (DenseHistogram.h:55-60).
+// variant the dense calls, which take the generator's rule in place of the box list and count by
+// sliding box sums); only the counts come back.  Frequencies are formed as
+// DenseHistogram::getFrequencies does (DenseHistogram.h:55-60).  The dense variant streams
+// (ife_bag_dense_stream_*): the device forms the frequencies too and delivers the bag in blocks of
+// rows that are written as they arrive.
 #ifndef IFE_HOST_BAGTOOL_H
 #define IFE_HOST_BAGTOOL_H
 
@@ -225,13 +227,65 @@ inline int bag_main(int argc, char *argv[], BagVariant variant, const char *tool
   if (!dense)
     for (const RegionType &roi : rois)
       for (int k = 0; k < 6; ++k) boxes.push_back(k < 3 ? roi.GetIndex()[k] : (int64_t)roi.GetSize()[k - 3]);
-  std::vector<uint32_t> counts(rois.size() * totalBins);
+  // The dense variant streams: the device forms the frequencies and delivers the bag in blocks of
+  // rows (ife_bag_dense_stream_*), each written as it arrives, so nothing of the size of the bag
+  // (rois.size() x totalBins words) exists on the host.  IFE_DENSE_BLOCK_MB bounds a block,
+  // IFE_DENSE_STREAM=0 keeps the whole-bag call.
+  const char *streamEnv = std::getenv("IFE_DENSE_STREAM");
+  const bool streamDense = dense && !rois.empty() && !(streamEnv && std::string(streamEnv) == "0");
+  const char *blockEnv = std::getenv("IFE_DENSE_BLOCK_MB");
+  const int blockMb = blockEnv && std::atoi(blockEnv) > 0 ? std::atoi(blockEnv) : 0;
+  const std::string outPath(Path::join(outDirPath, prefix + ".bag"));
+  std::ofstream out;
+  std::vector<uint32_t> counts(streamDense ? 0 : rois.size() * totalBins);
   for (size_t i = 0; i < scales.size(); ++i) std::cout << "Processing scale " << scales[i] << std::endl;
   try {
     ife::host::Engine &engine = ife::host::Engine::Instance();
     const ife_volume_desc d = ife::host::describe(*image);
     if (!dense && rois.size() > 0x7fffffff) throw itk::ExceptionObject("more than 2^31-1 regions", toolName);
-    if (!rois.empty() && dense) {
+    if (streamDense) {
+      const int64_t boxSize[3] = {(int64_t)roiSize[0], (int64_t)roiSize[1], (int64_t)roiSize[2]};
+      int64_t numRows = 0, maxBlockRows = 0, delivered = 0;
+      engine.check(ife_bag_dense_stream_begin(engine.ctx(), image->GetBufferPointer(), IFE_F32,
+                                              mask->GetBufferPointer(), IFE_U16,
+                                              roiMaskPath.empty() ? nullptr : roiMask->GetBufferPointer(), IFE_U16, &d,
+                                              scales.data(), (int)scales.size(), boxSize, edges.data(),
+                                              (int)(histSize - 1), IFE_BAG_FREQUENCIES, blockMb, &numRows,
+                                              &maxBlockRows, IFE_MEM_HOST),
+                   toolName);
+      std::ostringstream msg;
+      if (numRows != (int64_t)rois.size()) {  // .ROIInfo and .bag would disagree
+        msg << "the device counted " << numRows << " dense regions, the generator " << rois.size();
+        throw itk::ExceptionObject(msg.str().c_str(), toolName);
+      }
+      std::vector<PixelType> block((size_t)maxBlockRows * totalBins);
+      out.open(outPath.c_str());
+      for (;;) {
+        int64_t row0 = 0, blockRows = 0;
+        engine.check(ife_bag_dense_stream_next(engine.ctx(), block.data(), maxBlockRows, &row0, &blockRows), toolName);
+        if (blockRows == 0) break;
+        if (row0 != delivered) {
+          msg << "the device delivered row " << row0 << " where row " << delivered << " was due";
+          throw itk::ExceptionObject(msg.str().c_str(), toolName);
+        }
+        for (int64_t r = 0; r < blockRows; ++r) {
+          for (size_t h = 0; h < numHistograms; ++h) {
+            const PixelType *f = &block[((size_t)r * numHistograms + h) * histSize];
+            for (size_t b = 0; b < histSize; ++b) {
+              out << f[b];
+              if (h * histSize + b + 1 < totalBins) out << ",";
+            }
+          }
+          out << '\n';
+        }
+        delivered += blockRows;
+      }
+      engine.check(ife_bag_dense_stream_end(engine.ctx()), toolName);
+      if (delivered != numRows) {
+        msg << "the device delivered " << delivered << " rows, the generator counted " << rois.size();
+        throw itk::ExceptionObject(msg.str().c_str(), toolName);
+      }
+    } else if (!rois.empty() && dense) {
       const int64_t boxSize[3] = {(int64_t)roiSize[0], (int64_t)roiSize[1], (int64_t)roiSize[2]};
       int64_t numRows = 0;
       engine.check(ife_bag_image_dense(engine.ctx(), image->GetBufferPointer(), IFE_F32, mask->GetBufferPointer(),
@@ -259,9 +313,8 @@ inline int bag_main(int argc, char *argv[], BagVariant variant, const char *tool
     std::cerr << "Failed to update featureFilter." << std::endl << "ExceptionObject: " << e << std::endl;
     return EXIT_FAILURE;
   }
-  const std::string outPath(Path::join(outDirPath, prefix + ".bag"));
-  std::ofstream out(outPath.c_str());
-  for (size_t r = 0; r < rois.size(); ++r) {
+  if (!streamDense) out.open(outPath.c_str());
+  for (size_t r = 0; !streamDense && r < rois.size(); ++r) {
     for (size_t h = 0; h < numHistograms; ++h) {
       const uint32_t *c = &counts[(r * numHistograms + h) * histSize];
       int sum = 0;  // getFrequencies sums into an int, then divides floats

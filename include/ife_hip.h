@@ -109,7 +109,8 @@ typedef enum {
   /* Upper bound in MiB on the scratch of the dense bag calls (the planes of the box passes and,
    * in ife_bag_image_dense, the features of a group of scales): 0 (default) sizes the groups
    * from the free device memory.  Bins and scales then go through in smaller groups; results
-   * never change. */
+   * never change.  The dense bag stream takes its budget from it too (read by _begin): features,
+   * codes, and of the rest an eighth as the default bound of a block. */
   IFE_OPT_DENSE_SCRATCH_MB = 11,
   /* 1 (default): the first axis pass (Z) of ife_emphysema_features and of its streaming form
    * runs ONE causal sweep per line for all scales of a group, straight from image and mask (no
@@ -505,6 +506,51 @@ int ife_bag_image_dense(ife_ctx *ctx, const void *image, int image_dtype, const 
                         const ife_volume_desc *vol, const float *sigmas, int n_sigmas,
                         const int64_t size[3], const float *edges, int n_edges,
                         uint32_t *counts, int64_t capacity, int64_t *n_rois, int mem);
+
+/* The same bag as a stream of row blocks, for bags that fit neither the device nor the host in one
+ * piece.  Regions are numbered in raster order of their centres, so the regions whose centres lie
+ * in a run of z planes are a contiguous range of rows; a block is such a run of whole planes (at
+ * least one).  The device keeps the bin codes of all scales (one byte per voxel and column) and
+ * counts one block at a time from them.
+ *
+ * _begin: arguments, limits and checks of ife_bag_image_dense (mem describes image, mask and
+ * gen_mask; edges is a HOST array).  values: what _next delivers, the counts of
+ * ife_bag_image_dense (uint32_t) or the frequencies of DenseHistogram::getFrequencies (float:
+ * per histogram the counts summed into an int, then (float)count / (float)sum; an empty histogram
+ * is NaN in every bin, sign and payload unspecified).  block_mb bounds the bytes of one block,
+ * rows * n_sigmas*8 * (n_edges+1) * 4, in MiB (a single plane may exceed it); 0 takes the bound
+ * from the scratch budget (IFE_OPT_DENSE_SCRATCH_MB, or the free device memory).  Writes the
+ * number of regions to *n_rois and the row count of the largest block to *max_block_rows (both
+ * HOST scalars), so that the caller can size one array.  Uploads the inputs, runs the features of
+ * all scales and turns them into codes, plans the blocks and returns without waiting for any
+ * counting; HOST inputs may be reused when it returns, DEVICE inputs once the first _next has
+ * returned.  Zero regions (a box larger than the volume, too) is not an error: *n_rois = 0 and
+ * the first _next reports the end.  A stream that is still open is dropped.
+ *
+ * _next: delivers the blocks in row order into the HOST array `rows`, laid out as in
+ * ife_bag_image_dense: rows[(r - *row0) * n_sigmas*8 * (n_edges+1) + column * (n_edges+1) + bin]
+ * for the rows r in [*row0, *row0 + *n_rows).  *n_rows = 0 says that the stream is finished, and
+ * nothing else does.  capacity_rows smaller than the block: IFE_E_SIZE with *row0 and *n_rows
+ * set and nothing consumed; the call may be repeated with a larger array.  While the block is
+ * copied (on a copy stream of the stream's own) the next one is being counted.
+ *
+ * _end: frees what the stream holds on the device (also done by the next _begin and by
+ * ife_ctx_destroy).  _next or _end without a _begin: IFE_E_STATE.
+ *
+ * The stream owns every buffer it uses between the calls, so any other call on the context is
+ * legal between _begin and _end and does not change what the stream delivers.  Device memory:
+ * the codes (nvox * n_sigmas*8 bytes), three block buffers (one planar that the counting fills,
+ * two row-major on their way out) and the scratch of the box passes of one block. */
+typedef enum { IFE_BAG_COUNTS = 0, IFE_BAG_FREQUENCIES = 1 } ife_bag_values;
+int ife_bag_dense_stream_begin(ife_ctx *ctx, const void *image, int image_dtype, const void *mask,
+                               int mask_dtype, const void *gen_mask, int gen_mask_dtype,
+                               const ife_volume_desc *vol, const float *sigmas, int n_sigmas,
+                               const int64_t size[3], const float *edges, int n_edges,
+                               int values, int block_mb, int64_t *n_rois,
+                               int64_t *max_block_rows, int mem);
+int ife_bag_dense_stream_next(ife_ctx *ctx, void *rows, int64_t capacity_rows, int64_t *row0,
+                              int64_t *n_rows);
+int ife_bag_dense_stream_end(ife_ctx *ctx);
 
 /* The tool's `samples( scales.size() * numFeatures )` (:165-166): one growing column per
  * (scale, feature), kept in device memory.  Belongs to the context it was created on. */

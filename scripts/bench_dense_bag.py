@@ -9,7 +9,13 @@ Input: a synthetic float32 volume, the two-ellipsoid labels of synthetic.py, one
 edges of the foreground.  Both calls take host arrays and block, so a call is timed on the host
 clock: upload, features, counting and the copy of the counts back are all inside, for both.  The
 two count arrays must be equal.  Then the hipEvent time per kernel kind of one call of each
-(IFE_OPT_PROFILE).  Writes the result to --out and prints it as one JSON line."""
+(IFE_OPT_PROFILE).  Writes the result to --out and prints it as one JSON line.
+
+  python scripts/bench_dense_bag.py --stream [--out profiles/dense_stream.json]
+
+times, at the same configuration and in one process, ife_bag_image_dense (the yardstick) against
+the stream of row blocks (ife_bag_dense_stream_*) delivering frequencies: as one block, and with a
+bound of an eighth of the bag; per-kind kernel times of each."""
 import argparse
 import importlib
 import json
@@ -56,6 +62,88 @@ def kernel_ms(pkg, ctx, fn):
     return {k: {"launches": c, "total_ms": round(t, 4)} for k, (c, t) in kt.items()}
 
 
+def spread(times):
+    return {"median": round(statistics.median(times), 3), "min": round(min(times), 3), "max": round(max(times), 3)}
+
+
+def stream_mode(args, pkg, ctx, img, lab, sigmas, size, edges, dense):
+    """ife_bag_image_dense (the yardstick: the whole bag as counts in one host array) against the
+    stream of row blocks delivering frequencies, each block dropped as the next arrives: one block
+    (block_mb = 0) and a bound of an eighth of the bag."""
+    counts, t_dense = timed(dense, args.steps, args.warmup)
+    row_bytes = counts.shape[1] * counts.shape[2] * 4
+    eighth_mb = max(1, round(len(counts) * row_bytes / 8 / 2 ** 20))
+    s = counts.sum(-1, dtype=np.int32)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        want = np.float32(counts) / np.float32(s)[..., None]
+
+    def stream(block_mb, keep=False):
+        blocks = []
+        for row0, rows in ctx.bag_image_dense_stream(img, lab, sigmas, size, edges, block_mb=block_mb):
+            blocks.append((row0, rows) if keep else (row0, len(rows)))
+        return blocks
+
+    def phases(block_mb):
+        """Host-clock milliseconds of _begin, of all _next calls and of _end of one warm stream."""
+        import ctypes as C
+        lib = pkg.load_library()
+        d = pkg._desc(img.shape, (1.0, 1.0, 1.0))
+        e32 = np.ascontiguousarray(edges, np.float32)
+        n, cap, row0, got = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        t0 = time.perf_counter()
+        rc = lib.ife_bag_dense_stream_begin(ctx._h, img.ctypes.data, pkg.F32, lab.ctypes.data, pkg._MSK_DT[lab.dtype],
+                                            None, pkg.U8, C.byref(d), pkg._sigma_arg(sigmas), len(sigmas),
+                                            pkg._size_arg(size), e32.ctypes.data, e32.shape[1], pkg.BAG_FREQUENCIES,
+                                            block_mb, C.byref(n), C.byref(cap), pkg.MEM_HOST)
+        t1 = time.perf_counter()
+        rows = np.empty((max(cap.value, 1),) + counts.shape[1:], np.float32)
+        rows[:] = 0                                   # touched: no page fault inside the copies
+        t2 = time.perf_counter()
+        while rc == 0:
+            rc = lib.ife_bag_dense_stream_next(ctx._h, rows.ctypes.data, rows.shape[0], C.byref(row0), C.byref(got))
+            if got.value == 0:
+                break
+        t3 = time.perf_counter()
+        rc = rc or lib.ife_bag_dense_stream_end(ctx._h)
+        t4 = time.perf_counter()
+        if rc:
+            sys.exit("stream call failed: %d" % rc)
+        return {"begin": round((t1 - t0) * 1e3, 3), "next_all": round((t3 - t2) * 1e3, 3),
+                "end": round((t4 - t3) * 1e3, 3)}
+
+    runs, equal = {}, True
+    for name, block_mb in (("stream_one_block", 0), ("stream_eighths", eighth_mb)):
+        kept = stream(block_mb, keep=True)
+        got = np.concatenate([rows for _, rows in kept])
+        equal = equal and got.shape == want.shape and bool(
+            np.array_equal(got[s != 0].view(np.uint32), want[s != 0].view(np.uint32)) and np.isnan(got[s == 0]).all())
+        del kept, got
+        blocks, times = timed(lambda: stream(block_mb), args.steps, args.warmup)
+        runs[name] = {"block_mb": block_mb, "blocks": len(blocks), "largest_block_rows": max(n for _, n in blocks),
+                      "ms": spread(times), "phases_ms": phases(block_mb),
+                      "kernels": kernel_ms(pkg, ctx, lambda: stream(block_mb))}
+    ms_dense = statistics.median(t_dense)
+    out = {
+        "metric": "one image of MakeBagDense: ife_bag_image_dense (counts, whole bag) over the stream of row "
+                  "blocks (frequencies, one block), host arrays in and out",
+        "value": round(ms_dense / runs["stream_one_block"]["ms"]["median"], 2), "unit": "x",
+        "higher_is_better": True, "n_gpus": 1,
+        "shape": list(img.shape), "box": list(size), "bins": args.bins, "sigmas": sigmas,
+        "regions": int(len(counts)), "bag_bytes": int(len(counts) * row_bytes),
+        "steps": args.steps, "warmup": args.warmup, "data": "synthetic (two ellipsoids, unit spacing)",
+        "dense_ms": spread(t_dense), "dense_kernels": kernel_ms(pkg, ctx, dense),
+        "frequencies_equal": equal,
+    }
+    out.update(runs)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out), flush=True)
+    if not equal:
+        sys.exit("the streamed frequencies differ from those of the dense counts")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=96)
@@ -63,8 +151,11 @@ def main():
     ap.add_argument("--bins", type=int, default=9)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dense_bag.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--stream", action="store_true",
+                    help="time ife_bag_image_dense against the stream of row blocks (one block, about eight)")
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "dense_stream.json" if args.stream else "dense_bag.json")
     pkg = importlib.import_module(PKG)
     synth = importlib.import_module(PKG + ".synthetic")
     ctx = pkg.Context(0)   # raises when there is no gfx950 device: no number without a GPU
@@ -83,6 +174,8 @@ def main():
     def dense():
         return ctx.bag_image_dense(img, lab, sigmas, size, edges)
 
+    if args.stream:
+        return stream_mode(args, pkg, ctx, img, lab, sigmas, size, edges, dense)
     want, t_box = timed(per_box, args.steps, args.warmup)
     got, t_dense = timed(dense, args.steps, args.warmup)
     equal = bool(got.shape == want.shape and np.array_equal(got, want))
