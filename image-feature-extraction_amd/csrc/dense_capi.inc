@@ -43,37 +43,32 @@ struct DenseCentres {
 };
 
 // Flags and numbers the centres of `gen` (device) into `buf` (ctx->dn_centres, or the stream's
-// own); blocks for the count.
-int dense_centres(ife_ctx *ctx, const void *dG, int gen_dtype, const DenseGeom &g, DevBuf &buf, DenseCentres *out) {
+// own); blocks for the count, which goes to *n_rois as well.  More than `capacity` is an error.
+int dense_centres(ife_ctx *ctx, const void *dG, int gen_dtype, const DenseGeom &g, DevBuf &buf, int64_t capacity,
+                  int64_t *n_rois, DenseCentres *out) {
   const int64_t nseg = (int64_t)g.gx * g.ny * g.nz;
-  const int64_t nchunks = (nseg + SCAN_CHUNK - 1) / SCAN_CHUNK;
-  const size_t off_flag = (8 + (size_t)(nseg + nchunks) * 4 + 15) / 16 * 16;
-  int rc = ensure(ctx, buf, off_flag + (size_t)g.nvox);
+  int rc = ensure(ctx, buf, seg_scan_bytes(nseg) + (size_t)g.nvox);  // the flags stand behind the scan's own
   if (rc) return rc;
-  unsigned long long *ctr = (unsigned long long *)buf.p;
-  uint32_t *segs = (uint32_t *)((char *)buf.p + 8), *sums = segs + nseg;
-  uint8_t *flag = (uint8_t *)buf.p + off_flag;
+  uint32_t *segs = seg_counts(buf);
+  uint8_t *flag = (uint8_t *)buf.p + seg_scan_bytes(nseg);
   {
     ProfScope ps(ctx, KK_DENSE_CODE);
-    rc = with_mask_type(true, gen_dtype, dG, [&](auto gen) -> int {
+    with_mask_type(true, gen_dtype, dG, [&](auto gen) -> int {
       using TM = std::remove_cv_t<std::remove_pointer_t<decltype(gen)>>;
       hipLaunchKernelGGL(dense_centre_kernel<TM>, dim3(dense_blocks(nseg)), dim3(256), 0, ctx->stream, gen, flag,
                          segs, g, nseg);
       return IFE_OK;
     });
-    hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)nchunks), dim3(SORT_THREADS), 0, ctx->stream, segs, nseg, sums);
-    hipLaunchKernelGGL(scan_chunks_kernel, dim3(1), dim3(SORT_THREADS), 0, ctx->stream, sums, (int)nchunks, ctr);
-    hipLaunchKernelGGL(chunk_scan_kernel, dim3((unsigned)nchunks), dim3(SORT_THREADS), 0, ctx->stream, segs, nseg, sums);
-    IFE_HIP(ctx, hipGetLastError());
+    if ((rc = seg_scan(ctx, buf, nseg))) return rc;
   }
-  unsigned long long h = 0;
-  IFE_HIP(ctx, hipMemcpyAsync(&h, ctr, 8, hipMemcpyDeviceToHost, ctx->stream));
-  IFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
   out->flag = flag;
   out->seg_base = segs;
   out->nseg = nseg;
-  out->n = (int64_t)h;
-  return rc;
+  if ((rc = scan_total(ctx, buf, &out->n))) return rc;
+  *n_rois = out->n;
+  if (out->n > capacity)
+    return fail(ctx, IFE_E_SIZE, "%lld regions, the output holds %lld", (long long)out->n, (long long)capacity);
+  return IFE_OK;
 }
 
 // Bytes the caller may spend on scratch: IFE_OPT_DENSE_SCRATCH_MB when set, else four fifths of
@@ -211,8 +206,65 @@ int dense_hist_check(ife_ctx *ctx, const void *mask, int mask_dtype, const void 
   return IFE_OK;
 }
 
-int dense_too_many(ife_ctx *ctx, int64_t n, int64_t capacity) {
-  return fail(ctx, IFE_E_SIZE, "%lld regions, the output holds %lld", (long long)n, (long long)capacity);
+struct DenseInputs {       // the inputs of the histogram calls on the device
+  const void *mask, *gen;  // gen: the mask that generates the regions, with its dtype
+  int gen_dtype;
+  const float *edges;
+};
+
+// Stages the mask (st_mask) and, into st_aux, the generating mask (HOST mode) and the edges behind
+// it.  edges_mem: where the caller's edges are; IFE_MEM_DEVICE (so is `mem` then) leaves them in place.
+int dense_stage(ife_ctx *ctx, int mem, const void *mask, int mask_dtype, const void *gen_mask, int gen_mask_dtype,
+                size_t nvox, const float *edges, size_t ebytes, int edges_mem, DenseInputs *in) {
+  const size_t gbytes = gen_mask ? nvox * dtype_size(gen_mask_dtype) : 0, off_e = (gbytes + 15) / 16 * 16;
+  const void *dG = gen_mask;
+  int rc;
+  if ((rc = stage_in(ctx, mem, mask, nvox * dtype_size(mask_dtype), ctx->st_mask, &in->mask))) return rc;
+  in->edges = edges;
+  if (edges_mem == IFE_MEM_HOST) {
+    if ((rc = ensure(ctx, ctx->st_aux, off_e + ebytes))) return rc;
+    if (gen_mask && mem == IFE_MEM_HOST) {
+      IFE_HIP(ctx, hipMemcpyAsync(ctx->st_aux.p, gen_mask, gbytes, hipMemcpyHostToDevice, ctx->stream));
+      dG = ctx->st_aux.p;
+    }
+    in->edges = (const float *)((char *)ctx->st_aux.p + off_e);
+    IFE_HIP(ctx, hipMemcpyAsync((char *)ctx->st_aux.p + off_e, edges, ebytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  in->gen = dG ? dG : in->mask;
+  in->gen_dtype = dG ? gen_mask_dtype : mask_dtype;
+  return IFE_OK;
+}
+
+// Scales in groups: the clamped labels and the planar features of `sg` scales (32 bytes per voxel
+// and scale) live in dn_feat, labels first, and take at most `budget` (but one scale at least).
+struct DenseScalePlan { int sg; size_t off_f, fbytes; };
+DenseScalePlan dense_scale_plan(size_t budget, size_t nvox, int n_sigmas) {
+  const size_t scale_bytes = nvox * IFE_NUM_FEATURES * 4, off_f = (nvox + 15) / 16 * 16;
+  const int sg = (int)std::min<size_t>(std::max<size_t>(budget / scale_bytes, 1), (size_t)n_sigmas);
+  return {sg, off_f, off_f + (size_t)sg * scale_bytes};
+}
+
+// Clamps the labels once, then the features of every group of plan.sg scales into dn_feat and
+// each_scale(scale, its planar features, the clamped labels) for every scale of the group.
+template <typename F>
+int dense_scale_loop(ife_ctx *ctx, const void *dI, int image_dtype, const void *dM, int mask_dtype,
+                     const ife_volume_desc *vol, const float *sigmas, int n_sigmas, const DenseScalePlan &plan,
+                     F &&each_scale) {
+  const size_t nvox = (size_t)(vol->nx * vol->ny * vol->nz);
+  int rc = ensure(ctx, ctx->dn_feat, plan.fbytes);
+  if (rc) return rc;
+  uint8_t *clamp = (uint8_t *)ctx->dn_feat.p;
+  float *feat = (float *)((char *)ctx->dn_feat.p + plan.off_f);
+  if ((rc = launch_clamp01(ctx, dM, mask_dtype, clamp, (int64_t)nvox))) return rc;
+  for (int s0 = 0; s0 < n_sigmas; s0 += plan.sg) {
+    const int ns = std::min(plan.sg, n_sigmas - s0);
+    if ((rc = ife_emphysema_features(ctx, dI, image_dtype, clamp, IFE_U8, vol, sigmas + s0, ns, feat, IFE_PLANAR,
+                                     IFE_MEM_DEVICE)))
+      return rc;
+    for (int i = 0; i < ns; ++i)
+      if ((rc = each_scale(s0 + i, feat + (size_t)i * nvox * IFE_NUM_FEATURES, clamp))) return rc;
+  }
+  return IFE_OK;
 }
 
 }  // namespace
@@ -239,11 +291,9 @@ int ife_dense_rois(ife_ctx *ctx, const void *gen_mask, int gen_mask_dtype, const
   if (empty) return IFE_OK;
   const void *dG;
   if ((rc = stage_in(ctx, mem, gen_mask, (size_t)g.nvox * dtype_size(gen_mask_dtype), ctx->st_mask, &dG))) return rc;
-  DenseCentres cen;
-  if ((rc = dense_centres(ctx, dG, gen_mask_dtype, g, ctx->dn_centres, &cen))) return rc;
-  *n_rois = cen.n;
-  if (!rois || cen.n == 0) return IFE_OK;
-  if (cen.n > capacity) return dense_too_many(ctx, cen.n, capacity);
+  DenseCentres cen;  // without an array for the boxes the call counts only
+  rc = dense_centres(ctx, dG, gen_mask_dtype, g, ctx->dn_centres, rois ? capacity : INT64_MAX, n_rois, &cen);
+  if (rc || !rois || cen.n == 0) return rc;
   void *dR;
   if ((rc = stage_out_begin(ctx, mem, rois, (size_t)cen.n * 48, &dR))) return rc;
   {
@@ -281,31 +331,22 @@ int ife_dense_roi_histograms(ife_ctx *ctx, const float *features, int layout, in
   if ((rc = dense_geom(ctx, vol, size, true, &g, &empty))) return rc;
   *n_rois = 0;
   if (empty) return IFE_OK;
-  const size_t nvox = (size_t)g.nvox, gbytes = gen_mask ? nvox * dtype_size(gen_mask_dtype) : 0;
-  const size_t ebytes = (size_t)ncomp * n_edges * 4, off_e = (gbytes + 15) / 16 * 16;
-  const void *dM, *dG = nullptr, *dE = edges, *dF;
-  if ((rc = stage_in(ctx, mem, mask, nvox * dtype_size(mask_dtype), ctx->st_mask, &dM))) return rc;
-  if (mem == IFE_MEM_HOST) {  // the generating mask and the edges share one staging buffer
-    if ((rc = ensure(ctx, ctx->st_aux, off_e + ebytes))) return rc;
-    if (gen_mask) IFE_HIP(ctx, hipMemcpyAsync(ctx->st_aux.p, gen_mask, gbytes, hipMemcpyHostToDevice, ctx->stream));
-    IFE_HIP(ctx, hipMemcpyAsync((char *)ctx->st_aux.p + off_e, edges, ebytes, hipMemcpyHostToDevice, ctx->stream));
-    dG = gen_mask ? ctx->st_aux.p : nullptr;
-    dE = (char *)ctx->st_aux.p + off_e;
-  } else {
-    dG = gen_mask;
-  }
+  const size_t nvox = (size_t)g.nvox;
+  DenseInputs in;  // in DEVICE mode the caller's edges are read in place
+  if ((rc = dense_stage(ctx, mem, mask, mask_dtype, gen_mask, gen_mask_dtype, nvox, edges,
+                        (size_t)ncomp * n_edges * 4, mem, &in)))
+    return rc;
   DenseCentres cen;
-  if ((rc = dense_centres(ctx, dG ? dG : dM, dG ? gen_mask_dtype : mask_dtype, g, ctx->dn_centres, &cen))) return rc;
-  *n_rois = cen.n;
-  if (cen.n > capacity) return dense_too_many(ctx, cen.n, capacity);
-  if (cen.n == 0) return IFE_OK;
+  rc = dense_centres(ctx, in.gen, in.gen_dtype, g, ctx->dn_centres, capacity, n_rois, &cen);
+  if (rc || cen.n == 0) return rc;
+  const void *dF;
   if ((rc = stage_in(ctx, mem, features, nvox * ncomp * 4, ctx->st_img, &dF))) return rc;
   const size_t cbytes = (size_t)cen.n * ncomp * (n_edges + 1) * 4;
   void *dC;
   if ((rc = stage_out_begin(ctx, mem, counts, cbytes, &dC))) return rc;
   size_t budget;
   if ((rc = dense_budget(ctx, ctx->dn_ws.cap, &budget))) return rc;
-  if ((rc = dense_count(ctx, (const float *)dF, layout, ncomp, dM, mask_dtype, g, cen, (const float *)dE, n_edges,
+  if ((rc = dense_count(ctx, (const float *)dF, layout, ncomp, in.mask, mask_dtype, g, cen, in.edges, n_edges,
                         (uint32_t *)dC, (int64_t)ncomp * (n_edges + 1), 0, budget)))
     return rc;
   if (mem == IFE_MEM_DEVICE) {
@@ -334,49 +375,32 @@ int ife_bag_image_dense(ife_ctx *ctx, const void *image, int image_dtype, const 
   if ((rc = dense_geom(ctx, vol, size, true, &g, &empty))) return rc;
   *n_rois = 0;
   if (empty) return IFE_OK;
-  const size_t nvox = (size_t)g.nvox, gbytes = gen_mask ? nvox * dtype_size(gen_mask_dtype) : 0;
+  const size_t nvox = (size_t)g.nvox;
   const int ncol = n_sigmas * IFE_NUM_FEATURES, nb = n_edges + 1;
-  const size_t ebytes = (size_t)ncol * n_edges * 4, off_e = (gbytes + 15) / 16 * 16;
-  const void *dI, *dM, *dG = gen_mask;
-  if ((rc = stage_in(ctx, mem, mask, nvox * dtype_size(mask_dtype), ctx->st_mask, &dM))) return rc;
-  if ((rc = ensure(ctx, ctx->st_aux, off_e + ebytes))) return rc;  // generating mask (HOST mode), edges
-  if (gen_mask && mem == IFE_MEM_HOST) {
-    IFE_HIP(ctx, hipMemcpyAsync(ctx->st_aux.p, gen_mask, gbytes, hipMemcpyHostToDevice, ctx->stream));
-    dG = ctx->st_aux.p;
-  }
-  const float *dE = (const float *)((char *)ctx->st_aux.p + off_e);
-  IFE_HIP(ctx, hipMemcpyAsync((char *)ctx->st_aux.p + off_e, edges, ebytes, hipMemcpyHostToDevice, ctx->stream));
+  DenseInputs in;  // the edges are a host array in both modes
+  if ((rc = dense_stage(ctx, mem, mask, mask_dtype, gen_mask, gen_mask_dtype, nvox, edges,
+                        (size_t)ncol * n_edges * 4, IFE_MEM_HOST, &in)))
+    return rc;
+  // the image goes up only once there are regions to count, and not too many
   DenseCentres cen;
-  if ((rc = dense_centres(ctx, dG ? dG : dM, dG ? gen_mask_dtype : mask_dtype, g, ctx->dn_centres, &cen))) return rc;
-  *n_rois = cen.n;
-  if (cen.n > capacity) return dense_too_many(ctx, cen.n, capacity);
-  if (cen.n == 0) return IFE_OK;
+  rc = dense_centres(ctx, in.gen, in.gen_dtype, g, ctx->dn_centres, capacity, n_rois, &cen);
+  if (rc || cen.n == 0) return rc;
+  const void *dI;
   if ((rc = stage_in(ctx, mem, image, nvox * dtype_size(image_dtype), ctx->st_img, &dI))) return rc;
   const size_t cbytes = (size_t)cen.n * ncol * nb * 4;
   if ((rc = ensure(ctx, ctx->st_out, cbytes))) return rc;
-  // scales in groups: the clamped labels and the features of `sg` scales (32 bytes per voxel and
-  // scale) take at most half of the budget, the box counts get the rest
+  // the budget: at most half for the features of a group of scales, the box counts get the rest
   size_t budget;
   if ((rc = dense_budget(ctx, ctx->dn_ws.cap + ctx->dn_feat.cap, &budget))) return rc;
-  const size_t scale_bytes = nvox * IFE_NUM_FEATURES * 4, off_f = (nvox + 15) / 16 * 16;
-  const int sg = (int)std::min<size_t>(std::max<size_t>(budget / 2 / scale_bytes, 1), (size_t)n_sigmas);
-  const size_t fbytes = off_f + (size_t)sg * scale_bytes;
-  if ((rc = ensure(ctx, ctx->dn_feat, fbytes))) return rc;
-  uint8_t *clamp = (uint8_t *)ctx->dn_feat.p;
-  float *feat = (float *)((char *)ctx->dn_feat.p + off_f);
-  if ((rc = launch_clamp01(ctx, dM, mask_dtype, clamp, g.nvox))) return rc;
-  for (int s0 = 0; s0 < n_sigmas; s0 += sg) {
-    const int ns = std::min(sg, n_sigmas - s0);
-    if ((rc = ife_emphysema_features(ctx, dI, image_dtype, clamp, IFE_U8, vol, sigmas + s0, ns, feat, IFE_PLANAR,
-                                     IFE_MEM_DEVICE)))
-      return rc;
-    for (int i = 0; i < ns; ++i)
-      if ((rc = dense_count(ctx, feat + (size_t)i * nvox * IFE_NUM_FEATURES, IFE_PLANAR, IFE_NUM_FEATURES, clamp,
-                            IFE_U8, g, cen, dE + (size_t)(s0 + i) * IFE_NUM_FEATURES * n_edges, n_edges,
-                            (uint32_t *)ctx->st_out.p, (int64_t)ncol * nb, (int64_t)(s0 + i) * IFE_NUM_FEATURES * nb,
-                            budget > fbytes ? budget - fbytes : 0)))
-        return rc;
-  }
+  const DenseScalePlan plan = dense_scale_plan(budget / 2, nvox, n_sigmas);
+  const size_t rest = budget > plan.fbytes ? budget - plan.fbytes : 0;
+  auto count_scale = [&](int s, const float *feat, const uint8_t *clamp) {  // into its block of columns
+    return dense_count(ctx, feat, IFE_PLANAR, IFE_NUM_FEATURES, clamp, IFE_U8, g, cen,
+                       in.edges + (size_t)s * IFE_NUM_FEATURES * n_edges, n_edges, (uint32_t *)ctx->st_out.p,
+                       (int64_t)ncol * nb, (int64_t)s * IFE_NUM_FEATURES * nb, rest);
+  };
+  if ((rc = dense_scale_loop(ctx, dI, image_dtype, in.mask, mask_dtype, vol, sigmas, n_sigmas, plan, count_scale)))
+    return rc;
   IFE_HIP(ctx, hipMemcpyAsync(counts, ctx->st_out.p, cbytes, hipMemcpyDeviceToHost, ctx->stream));
   IFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return IFE_OK;
@@ -397,21 +421,12 @@ void dense_stream_release(ife_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     if (ds.copy) (void)hipStreamSynchronize(ds.copy);
   }
-  for (DevBuf *b : {&ds.codes, &ds.centres, &ds.ws, &ds.planar, &ds.rows[0], &ds.rows[1]})
-    if (b->p) {
-      (void)hipFree(b->p);
-      b->p = nullptr;
-      b->cap = 0;
-    }
-  for (auto &e : ds.done)
-    if (e) {
-      (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-  ds.blocks.clear();
-  ds.next = ds.counted = 0;
-  ds.n_rois = 0;
-  ds.open = false;
+  for (auto e : ds.done)
+    if (e) (void)hipEventDestroy(e);
+  // a fresh stream state frees every buffer of the old one; the copy stream lives on with the context
+  const hipStream_t copy = ds.copy;
+  ds = ife_ctx::DenseStream();
+  ds.copy = copy;
 }
 
 // Enqueues block k: the box passes from the codes of its planes into the planar buffer, then the
@@ -458,26 +473,20 @@ int dense_stream_begin(ife_ctx *ctx, const void *image, int image_dtype, const v
                        int64_t *max_block_rows, int mem) {
   auto &ds = ctx->ds;
   int rc;
-  const size_t nvox = (size_t)g.nvox, gbytes = gen_mask ? nvox * dtype_size(gen_mask_dtype) : 0;
+  const size_t nvox = (size_t)g.nvox;
   const int ncol = n_sigmas * IFE_NUM_FEATURES, nb = n_edges + 1;
-  const size_t ebytes = (size_t)ncol * n_edges * 4, off_e = (gbytes + 15) / 16 * 16;
-  // 1. uploads (all of them before the count of the centres comes back, which waits for them: the
-  // caller may reuse its host arrays once _begin returns)
-  const void *dI, *dM, *dG = gen_mask;
-  if ((rc = stage_in(ctx, mem, mask, nvox * dtype_size(mask_dtype), ctx->st_mask, &dM))) return rc;
-  if ((rc = ensure(ctx, ctx->st_aux, off_e + ebytes))) return rc;  // generating mask (HOST mode), edges
-  if (gen_mask && mem == IFE_MEM_HOST) {
-    IFE_HIP(ctx, hipMemcpyAsync(ctx->st_aux.p, gen_mask, gbytes, hipMemcpyHostToDevice, ctx->stream));
-    dG = ctx->st_aux.p;
-  }
-  const float *dE = (const float *)((char *)ctx->st_aux.p + off_e);
-  IFE_HIP(ctx, hipMemcpyAsync((char *)ctx->st_aux.p + off_e, edges, ebytes, hipMemcpyHostToDevice, ctx->stream));
+  // every upload before the count of the centres comes back, which waits for them: the caller may
+  // reuse its host arrays once _begin returns
+  DenseInputs in;
+  const void *dI;
+  if ((rc = dense_stage(ctx, mem, mask, mask_dtype, gen_mask, gen_mask_dtype, nvox, edges,
+                        (size_t)ncol * n_edges * 4, IFE_MEM_HOST, &in)))
+    return rc;
   if ((rc = stage_in(ctx, mem, image, nvox * dtype_size(image_dtype), ctx->st_img, &dI))) return rc;
-  // 3. the centres, and per centre plane the number of its first region
+  // the centres, and per centre plane the number of its first region
   DenseCentres cen;
-  if ((rc = dense_centres(ctx, dG ? dG : dM, dG ? gen_mask_dtype : mask_dtype, g, ds.centres, &cen))) return rc;
-  ds.n_rois = cen.n;
-  if (cen.n == 0) return IFE_OK;
+  rc = dense_centres(ctx, in.gen, in.gen_dtype, g, ds.centres, INT64_MAX, &ds.n_rois, &cen);
+  if (rc || cen.n == 0) return rc;
   const int64_t nplanes = g.nz - g.sz + 1;
   std::vector<uint32_t> first((size_t)nplanes);
   if ((rc = ensure(ctx, ctx->st_out, (size_t)nplanes * 4))) return rc;
@@ -496,10 +505,9 @@ int dense_stream_begin(ife_ctx *ctx, const void *image, int image_dtype, const v
   // and of the rest an eighth per block buffer (three of them) and half for the box passes
   size_t budget;
   if ((rc = dense_budget(ctx, ctx->dn_feat.cap, &budget))) return rc;
-  const size_t scale_bytes = nvox * IFE_NUM_FEATURES * 4, off_f = (nvox + 15) / 16 * 16;
-  const int sg = (int)std::min<size_t>(std::max<size_t>(budget / 2 / scale_bytes, 1), (size_t)n_sigmas);
-  const size_t fbytes = off_f + (size_t)sg * scale_bytes, cbytes = (size_t)ncol * nvox;
-  const size_t rest = budget > fbytes + cbytes ? budget - fbytes - cbytes : 0;
+  const DenseScalePlan plan = dense_scale_plan(budget / 2, nvox, n_sigmas);
+  const size_t cbytes = (size_t)ncol * nvox;
+  const size_t rest = budget > plan.fbytes + cbytes ? budget - plan.fbytes - cbytes : 0;
   const size_t row_bytes = (size_t)ncol * nb * 4;
   ds.blocks = dense_plan(plane_rows, row_bytes, block_mb > 0 ? (size_t)block_mb << 20 : rest / 8, g.sz);
   int64_t max_rows = 0, max_planes = 0;
@@ -515,7 +523,6 @@ int dense_stream_begin(ife_ctx *ctx, const void *image, int image_dtype, const v
   ds.ncol = ncol;
   ds.nb = nb;
   ds.ld = (max_rows + 63) / 64 * 64;
-  if ((rc = ensure(ctx, ctx->dn_feat, fbytes))) return rc;
   if ((rc = ensure(ctx, ds.codes, cbytes))) return rc;
   if ((rc = ensure(ctx, ds.ws, bvox * 3 * ds.cg * ds.bg))) return rc;
   if ((rc = ensure(ctx, ds.planar, (size_t)ds.ld * row_bytes))) return rc;
@@ -524,21 +531,13 @@ int dense_stream_begin(ife_ctx *ctx, const void *image, int image_dtype, const v
     IFE_HIP(ctx, hipEventCreateWithFlags(&ds.done[i], hipEventDisableTiming));
   }
   if (!ds.copy) IFE_HIP(ctx, hipStreamCreateWithFlags(&ds.copy, hipStreamNonBlocking));
-  // 2., 4., 5. clamped labels, the features of a group of scales, their codes; the features go
-  uint8_t *clamp = (uint8_t *)ctx->dn_feat.p;
-  float *feat = (float *)((char *)ctx->dn_feat.p + off_f);
-  if ((rc = launch_clamp01(ctx, dM, mask_dtype, clamp, g.nvox))) return rc;
-  for (int s0 = 0; s0 < n_sigmas; s0 += sg) {
-    const int ns = std::min(sg, n_sigmas - s0);
-    if ((rc = ife_emphysema_features(ctx, dI, image_dtype, clamp, IFE_U8, vol, sigmas + s0, ns, feat, IFE_PLANAR,
-                                     IFE_MEM_DEVICE)))
-      return rc;
-    for (int i = 0; i < ns; ++i)
-      if ((rc = dense_code(ctx, feat + (size_t)i * nvox * IFE_NUM_FEATURES, g.nvox, 1, 0, IFE_NUM_FEATURES, clamp,
-                           IFE_U8, g.nvox, dE + (size_t)(s0 + i) * IFE_NUM_FEATURES * n_edges, n_edges,
-                           (uint8_t *)ds.codes.p + (size_t)(s0 + i) * IFE_NUM_FEATURES * nvox)))
-        return rc;
-  }
+  auto code_scale = [&](int s, const float *feat, const uint8_t *clamp) {  // only the codes stay
+    return dense_code(ctx, feat, g.nvox, 1, 0, IFE_NUM_FEATURES, clamp, IFE_U8, g.nvox,
+                      in.edges + (size_t)s * IFE_NUM_FEATURES * n_edges, n_edges,
+                      (uint8_t *)ds.codes.p + (size_t)s * IFE_NUM_FEATURES * nvox);
+  };
+  if ((rc = dense_scale_loop(ctx, dI, image_dtype, in.mask, mask_dtype, vol, sigmas, n_sigmas, plan, code_scale)))
+    return rc;
   *max_block_rows = max_rows;
   return dense_stream_count(ctx, 0);  // the first block is under way when _begin returns
 }

@@ -104,9 +104,28 @@ const char *kKindNames[KK_COUNT] = {"iir_z", "iir_x", "iir_y", "zslab_sweep", "z
                                     "sort_scatter", "gather", "edges", "dense_histogram", "edt_x", "edt_y",
                                     "edt_z", "edt_reduce", "dense_code", "dense_box_xy", "dense_box_z", "jet_features"};
 
+// A device allocation and its owner: move-only, freed by reset() or the destructor (hipFree finds
+// the allocation's device, whichever is current).
 struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  // by exchange: the old allocation is freed with o
+  DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+  ~DevBuf() { (void)reset(); }
+  hipError_t reset() {
+    cap = 0;
+    return p ? hipFree(std::exchange(p, nullptr)) : hipSuccess;
+  }
+  // A fresh allocation in place of the old one, whose contents go; nothing in flight may still
+  // use the old one (the caller sees to that).
+  hipError_t grow(size_t bytes) {
+    hipError_t e = reset();
+    if (e == hipSuccess && (e = hipMalloc(&p, bytes)) == hipSuccess) cap = bytes;
+    else p = nullptr;
+    return e;
+  }
 };
 constexpr int IFE_MAX_SLOTS = 3;
 
@@ -205,14 +224,8 @@ int fail(ife_ctx *ctx, int code, const char *fmt, ...) {
 
 int ensure(ife_ctx *ctx, DevBuf &b, size_t bytes) {
   if (b.cap >= bytes) return IFE_OK;
-  if (b.p) {
-    IFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    IFE_HIP(ctx, hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-  }
-  IFE_HIP(ctx, hipMalloc(&b.p, bytes));
-  b.cap = bytes;
+  if (b.p) IFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  IFE_HIP(ctx, b.grow(bytes));
   return IFE_OK;
 }
 
@@ -1114,18 +1127,9 @@ void ife_ctx_destroy(ife_ctx *ctx) {
   if (ctx->sc_copy) (void)hipStreamDestroy(ctx->sc_copy);
   dense_stream_release(ctx);
   if (ctx->ds.copy) (void)hipStreamDestroy(ctx->ds.copy);
-  std::vector<DevBuf *> bufs = {&ctx->pre[0], &ctx->pre[1], &ctx->st_img, &ctx->st_mask,
-                                &ctx->st_aux, &ctx->st_out, &ctx->sc_out, &ctx->edt_g,
-                                &ctx->edt_i, &ctx->edt_d2, &ctx->edt_part, &ctx->dn_centres,
-                                &ctx->dn_ws, &ctx->dn_feat, &ctx->dj_ws, &ctx->zs_rec};
-  for (auto &sl : ctx->fld)
-    for (auto &b : sl) bufs.push_back(&b);
-  for (auto &b : ctx->ck_y) bufs.push_back(&b);
-  for (DevBuf *b : bufs)
-    if (b->p) (void)hipFree(b->p);
   for (auto &r : ctx->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
   for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
-  delete ctx;
+  delete ctx;  // every DevBuf of the context frees itself here, behind the events and streams
 }
 
 const char *ife_last_error(const ife_ctx *ctx) {
@@ -1377,11 +1381,7 @@ int ife_emphysema_features_end(ife_ctx *ctx) {
   if (ctx->sc_copy) IFE_HIP(ctx, hipStreamSynchronize(ctx->sc_copy));
   for (auto e : ctx->sc_done) (void)hipEventDestroy(e);
   ctx->sc_done.clear();
-  if (ctx->sc_out.p) {
-    IFE_HIP(ctx, hipFree(ctx->sc_out.p));
-    ctx->sc_out.p = nullptr;
-    ctx->sc_out.cap = 0;
-  }
+  IFE_HIP(ctx, ctx->sc_out.reset());
   ctx->sc_scale_bytes = 0;
   return IFE_OK;
 }
@@ -1662,22 +1662,24 @@ int ife_measure_stream(ife_ctx *ctx, int mode, void *dst, const void *src, size_
   const int64_t n4 = (int64_t)(bytes / 16);
   // one piece per thread: the fastest shape on this chip (see launch_prep)
   const unsigned blocks = (unsigned)std::min<int64_t>((n4 + 255) / 256, 0x7fffffff);
-  hipEvent_t a, b;
-  IFE_HIP(ctx, hipEventCreate(&a));
-  IFE_HIP(ctx, hipEventCreate(&b));
   auto launch = [&]() {
     if (mode == 0) hipLaunchKernelGGL(stream_fill_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (float4 *)dst, n4, 1.0f);
     else hipLaunchKernelGGL(stream_copy_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const float4 *)src, (float4 *)dst, n4);
   };
-  launch();  // warm
-  (void)hipEventRecord(a, ctx->stream);
-  for (int i = 0; i < reps; ++i) launch();
-  (void)hipEventRecord(b, ctx->stream);
-  hipError_t e = hipEventSynchronize(b);
+  hipEvent_t a = nullptr, b = nullptr;
+  hipError_t e = hipEventCreate(&a);
+  if (e == hipSuccess) e = hipEventCreate(&b);
   float ms = 0.f;
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
+  if (e == hipSuccess) {
+    launch();  // warm
+    (void)hipEventRecord(a, ctx->stream);
+    for (int i = 0; i < reps; ++i) launch();
+    (void)hipEventRecord(b, ctx->stream);
+    e = hipEventSynchronize(b);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
+  }
+  if (a) (void)hipEventDestroy(a);  // whatever was created, on every path
+  if (b) (void)hipEventDestroy(b);
   if (e != hipSuccess) return fail(ctx, IFE_E_HIP, "stream measurement: %s", hipGetErrorString(e));
   *ms_per_pass = (double)ms / reps;
   return IFE_OK;

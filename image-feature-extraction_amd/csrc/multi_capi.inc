@@ -70,11 +70,7 @@ int mfail(ife_multi *m, int code, const char *fmt, ...) {
 int mensure(ife_multi *m, MultiRank &R, DevBuf &b, size_t bytes) {
   if (b.cap >= bytes) return IFE_OK;
   IFE_MHIP(m, hipSetDevice(R.dev));
-  if (b.p) IFE_MHIP(m, hipFree(b.p));
-  b.p = nullptr;
-  b.cap = 0;
-  IFE_MHIP(m, hipMalloc(&b.p, bytes));
-  b.cap = bytes;
+  IFE_MHIP(m, b.grow(bytes));
   return IFE_OK;
 }
 
@@ -106,24 +102,18 @@ int mcopy(ife_multi *m, MultiRank &from, hipStream_t s, MultiRank &to, void *dst
 
 void mfree_rank(MultiRank &R) {
   (void)hipSetDevice(R.dev);
-  if (R.sb) (void)hipStreamSynchronize(R.sb);
-  if (R.sc) (void)hipStreamSynchronize(R.sc);
-  if (R.sd) (void)hipStreamSynchronize(R.sd);
+  const hipStream_t streams[3] = {R.sb, R.sc, R.sd};
+  for (hipStream_t s : streams)
+    if (s) (void)hipStreamSynchronize(s);
   for (auto e : R.ev) (void)hipEventDestroy(e);
-  R.ev.clear();
-  R.uploaded = nullptr;
-  std::vector<DevBuf *> bufs = {&R.img, &R.mask, &R.src[0], &R.src[1], &R.out};
-  for (auto *v : {&R.zo, &R.xo, &R.pad, &R.ck, &R.c_in, &R.c_out, &R.a_in, &R.a_out})
-    for (auto &b : *v) bufs.push_back(&b);
-  for (DevBuf *b : bufs)
-    if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
-  if (R.bulk) ife_ctx_destroy(R.bulk);
-  if (R.chain) ife_ctx_destroy(R.chain);
-  if (R.sb) (void)hipStreamDestroy(R.sb);
-  if (R.sc) (void)hipStreamDestroy(R.sc);
-  if (R.sd) (void)hipStreamDestroy(R.sd);
-  R.bulk = R.chain = nullptr;
-  R.sb = R.sc = R.sd = nullptr;
+  // the rank's own buffers go first (an empty rank in its place frees every DevBuf of it), then
+  // its two contexts, its streams last
+  ife_ctx *const bulk = R.bulk, *const chain = R.chain;
+  R = MultiRank();
+  if (bulk) ife_ctx_destroy(bulk);
+  if (chain) ife_ctx_destroy(chain);
+  for (hipStream_t s : streams)
+    if (s) (void)hipStreamDestroy(s);
 }
 
 #define IFE_MCTX(m, R, c, call)                                                     \

@@ -93,19 +93,41 @@ int samples_reserve(ife_samples *s, int64_t need) {
   ife_ctx *ctx = s->ctx;
   if (need <= s->cap) return IFE_OK;
   const int64_t cap = std::max<int64_t>({need, 2 * s->cap, 4096});
-  DevBuf nd;
-  IFE_HIP(ctx, hipMalloc(&nd.p, (size_t)cap * s->ncol * 4));
-  nd.cap = (size_t)cap * s->ncol * 4;
+  DevBuf nd;  // frees itself where a step below fails
+  IFE_HIP(ctx, nd.grow((size_t)cap * s->ncol * 4));
   for (int c = 0; c < s->ncol; ++c)
     if (s->count[c] > 0)
       IFE_HIP(ctx, hipMemcpyAsync((float *)nd.p + (size_t)c * cap, (float *)s->data.p + (size_t)c * s->cap,
                                   (size_t)s->count[c] * 4, hipMemcpyDeviceToDevice, ctx->stream));
   IFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (s->data.p) IFE_HIP(ctx, hipFree(s->data.p));
-  if (s->tmp.p) IFE_HIP(ctx, hipFree(s->tmp.p));
-  s->data = nd;
-  s->tmp = DevBuf();
+  IFE_HIP(ctx, s->data.reset());
+  IFE_HIP(ctx, s->tmp.reset());
+  s->data = std::move(nd);
   s->cap = cap;
+  return IFE_OK;
+}
+
+// The exclusive scan of nseg segment counts, in place: [8-byte counter][nseg counts][nchunks chunk
+// sums], seg_scan_bytes() rounded to 16 for what a caller keeps behind.  The caller's code kernel writes
+// the counts, seg_scan() follows under the same ProfScope, scan_total() reads the counter back (blocks).
+int64_t seg_scan_chunks(int64_t nseg) { return (nseg + SCAN_CHUNK - 1) / SCAN_CHUNK; }
+size_t seg_scan_bytes(int64_t nseg) { return (8 + (size_t)(nseg + seg_scan_chunks(nseg)) * 4 + 15) / 16 * 16; }
+uint32_t *seg_counts(const DevBuf &b) { return (uint32_t *)((char *)b.p + 8); }
+int seg_scan(ife_ctx *ctx, const DevBuf &b, int64_t nseg) {
+  const int64_t nchunks = seg_scan_chunks(nseg);
+  uint32_t *segs = seg_counts(b), *sums = segs + nseg;
+  hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)nchunks), dim3(SORT_THREADS), 0, ctx->stream, segs, nseg, sums);
+  hipLaunchKernelGGL(scan_chunks_kernel, dim3(1), dim3(SORT_THREADS), 0, ctx->stream, sums, (int)nchunks,
+                     (unsigned long long *)b.p);
+  hipLaunchKernelGGL(chunk_scan_kernel, dim3((unsigned)nchunks), dim3(SORT_THREADS), 0, ctx->stream, segs, nseg, sums);
+  IFE_HIP(ctx, hipGetLastError());
+  return IFE_OK;
+}
+int scan_total(ife_ctx *ctx, const DevBuf &b, int64_t *total) {
+  unsigned long long h = 0;
+  IFE_HIP(ctx, hipMemcpyAsync(&h, b.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+  IFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *total = (int64_t)h;
   return IFE_OK;
 }
 
@@ -129,7 +151,7 @@ int add_features_typed(ife_ctx *ctx, ife_samples *s, int first, const float *dF,
   int rc = ensure(ctx, s->counter, 8 + (size_t)nchunks * 4);
   if (rc) return rc;
   unsigned long long *ctr = (unsigned long long *)s->counter.p;
-  uint32_t *chunks = (uint32_t *)((char *)s->counter.p + 8);
+  uint32_t *chunks = seg_counts(s->counter);  // here one count per chunk: only their scan is needed
   int64_t add = n_idx;
   if (!dIdx) {
     {
@@ -137,10 +159,7 @@ int add_features_typed(ife_ctx *ctx, ife_samples *s, int first, const float *dF,
       hipLaunchKernelGGL(count_foreground_kernel<TM>, dim3((unsigned)nchunks), dim3(256), 0, ctx->stream, dM, a, chunks);
       hipLaunchKernelGGL(scan_chunks_kernel, dim3(1), dim3(SORT_THREADS), 0, ctx->stream, chunks, nchunks, ctr);
     }
-    unsigned long long h = 0;
-    IFE_HIP(ctx, hipMemcpyAsync(&h, ctr, 8, hipMemcpyDeviceToHost, ctx->stream));
-    IFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    add = (int64_t)h;
+    if ((rc = scan_total(ctx, s->counter, &add))) return rc;
   }
   if (add == 0) return IFE_OK;
   if ((rc = samples_reserve(s, have + add))) return rc;
@@ -413,10 +432,7 @@ void ife_samples_destroy(ife_samples *s) {
   if (!s) return;
   (void)hipSetDevice(s->ctx->device);
   (void)hipStreamSynchronize(s->ctx->stream);
-  for (DevBuf *b : {&s->data, &s->tmp, &s->table, &s->totals, &s->feat, &s->clamp, &s->idx,
-                    &s->counter, &s->edges, &s->status})
-    if (b->p) (void)hipFree(b->p);
-  delete s;
+  delete s;  // its DevBufs free themselves
 }
 
 int ife_samples_count(const ife_samples *s, int column, int64_t *n) {
@@ -520,12 +536,9 @@ int ife_samples_add_image(ife_ctx *ctx, ife_samples *s, const void *image, int i
     if (nvox >= ((int64_t)1 << 32))
       return fail(ctx, IFE_E_SIZE, "volume too large for 32-bit sample offsets");
     if ((rc = ensure(ctx, s->feat, (size_t)nvox))) return rc;                 // the per-voxel code
-    const int64_t nchunks = (nseg + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    if ((rc = ensure(ctx, s->counter, 8 + (size_t)(nseg + nchunks) * 4))) return rc;
+    if ((rc = ensure(ctx, s->counter, seg_scan_bytes(nseg)))) return rc;
     uint8_t *code = (uint8_t *)s->feat.p;
-    unsigned long long *ctr = (unsigned long long *)s->counter.p;
-    uint32_t *segs = (uint32_t *)((char *)s->counter.p + 8);
-    uint32_t *sums = segs + nseg;
+    uint32_t *segs = seg_counts(s->counter);
     {
       ProfScope ps(ctx, KK_GATHER);
       const unsigned sb = (unsigned)std::min<int64_t>((nseg + 3) / 4, 32768);
@@ -535,17 +548,13 @@ int ife_samples_add_image(ife_ctx *ctx, ife_samples *s, const void *image, int i
                            (int)vol->nx, gx, nseg, a);
         return IFE_OK;
       });
-      hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)nchunks), dim3(SORT_THREADS), 0, ctx->stream, segs, nseg, sums);
-      hipLaunchKernelGGL(scan_chunks_kernel, dim3(1), dim3(SORT_THREADS), 0, ctx->stream, sums, (int)nchunks, ctr);
-      hipLaunchKernelGGL(chunk_scan_kernel, dim3((unsigned)nchunks), dim3(SORT_THREADS), 0, ctx->stream, segs, nseg, sums);
-      IFE_HIP(ctx, hipGetLastError());
+      if ((rc = seg_scan(ctx, s->counter, nseg))) return rc;
     }
-    unsigned long long h = 0;
-    IFE_HIP(ctx, hipMemcpyAsync(&h, ctr, 8, hipMemcpyDeviceToHost, ctx->stream));
-    IFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    int64_t h = 0;
+    if ((rc = scan_total(ctx, s->counter, &h))) return rc;
     if (h == 0) return IFE_OK;
     const int64_t have = s->count[0];
-    if ((rc = samples_reserve(s, have + (int64_t)h))) return rc;
+    if ((rc = samples_reserve(s, have + h))) return rc;
     SampleSink sink;
     sink.code = code;
     sink.seg_base = segs;
@@ -556,7 +565,7 @@ int ife_samples_add_image(ife_ctx *ctx, ife_samples *s, const void *image, int i
       return emphysema_typed(ctx, img, cm, vol, sigmas, n_sigmas, nullptr, IFE_PLANAR, &sink);
     });
     if (rc) return rc;
-    for (int c = 0; c < s->ncol; ++c) s->count[c] = have + (int64_t)h;
+    for (int c = 0; c < s->ncol; ++c) s->count[c] = have + h;
     s->sorted = false;
     return IFE_OK;
   }
