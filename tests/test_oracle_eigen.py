@@ -91,6 +91,31 @@ def test_float_solver_tracks_double_solver(oracle):
     assert d.max() < 5e-6  # the two include contexts (SURVEY TL;DR item 5)
 
 
+def test_float_solver_is_finite_and_scale_covariant_where_the_gpu_tests_need_it(oracle):
+    """The facts tests/test_gpu_solver_range.py leans on: 4096 normal rows times 2^k through the
+    float solver in the double context.  Scaling by a power of two is exact, so as long as no
+    intermediate leaves the normal range the triple of A * 2^k is ldexp(triple of A, k) bit
+    for bit.  Measured here:
+      k in [-51, 61]   every row exactly covariant
+      k = -60, -61, -62   99.9 %, 99.2 %, 95.8 % of the rows still are (p0 and d*d go denormal);
+                       finite, and accurate to 1.1e-6 |lambda_1|, down to k = -63
+      k = 62, 63, 66   p2 overflows: 9 %, 76 %, 100 % of the rows are inf/NaN
+    so every device guard (2^+-50 for mode 2, 2^+-60 for modes 0 and 1) lies where the
+    reference is finite and exact."""
+    A = np.random.default_rng(3).standard_normal((4096, 6)).astype(np.float32)
+    ev = oracle.eig3(A, 0)
+    assert np.isfinite(ev).all()
+    for k in range(-63, 62):
+        got = oracle.eig3(np.ldexp(A, k).astype(np.float32), 0)
+        assert np.isfinite(got).all(), k
+        if k >= -51:
+            assert np.array_equal(got.view(np.uint32), np.ldexp(ev, k).astype(np.float32).view(np.uint32)), k
+    with np.errstate(over="ignore"):
+        bad = {k: float((~np.isfinite(oracle.eig3(np.ldexp(A, k).astype(np.float32), 0)).all(-1)).mean())
+               for k in (62, 63, 66)}
+    assert 0.05 < bad[62] < 0.15 and 0.6 < bad[63] < 0.9 and bad[66] == 1.0, bad
+
+
 def test_features_functor(oracle):
     rng = np.random.default_rng(13)
     A = rng.standard_normal((100, 6)).astype(np.float32)
