@@ -31,6 +31,7 @@ OPT_CONST_LINES = 9
 OPT_FEAT_RING = 10
 OPT_DENSE_SCRATCH_MB = 11
 OPT_Z_SWEEP = 12
+OPT_DIFFERENTIAL = 13  # 1: the composite calls take their features from the jet (include/ife_hip.h)
 BAG_COUNTS, BAG_FREQUENCIES = 0, 1  # ife_bag_values: what the dense bag stream delivers
 Z_STATE_BYTES = 32   # IFE_Z_STATE_BYTES: one state record of the slab Z pass, per line and job
 Z_OVERLAP_LO, Z_OVERLAP_HI = 3, 4  # IFE_Z_OVERLAP_*: neighbour planes around a slab's input

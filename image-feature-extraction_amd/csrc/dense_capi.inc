@@ -267,6 +267,34 @@ int dense_scale_loop(ife_ctx *ctx, const void *dI, int image_dtype, const void *
   return IFE_OK;
 }
 
+// IFE_OPT_DIFFERENTIAL: no feature volume.  The clamped labels stand at the start of dn_feat
+// (`fbytes` of it are ensured: the caller may keep more behind them); per scale the twenty fields of
+// the jet, then the eight code planes straight from them to code_of(scale) ([8][nvox] bytes), then
+// each_scale(scale, those planes, the clamped labels).  dEdges: [n_sigmas * 8][n_edges], device.
+template <typename C, typename F>
+int dense_jet_scales(ife_ctx *ctx, const void *dI, int image_dtype, const void *dM, int mask_dtype,
+                     const ife_volume_desc *vol, const float *sigmas, int n_sigmas, const float *dEdges, int n_edges,
+                     size_t fbytes, C &&code_of, F &&each_scale) {
+  const int64_t nvox = vol->nx * vol->ny * vol->nz;
+  int rc = ensure(ctx, ctx->dn_feat, fbytes);
+  if (rc) return rc;
+  uint8_t *clamp = (uint8_t *)ctx->dn_feat.p;
+  if ((rc = launch_clamp01(ctx, dM, mask_dtype, clamp, nvox))) return rc;
+  if (reinterpret_cast<uintptr_t>(dI) % dtype_size(image_dtype))
+    return fail(ctx, IFE_E_ARG, "input pointers must be aligned to their element size");
+  return with_types(image_dtype, dI, true, IFE_U8, clamp, [&](auto img, auto cm) {
+    int r = jet_sources(ctx, img, cm, nvox);
+    for (int s = 0; s < n_sigmas && !r; ++s) {
+      JetFields f;
+      r = jet_fields(ctx, (const float *)ctx->pre[0].p, (const float *)ctx->pre[1].p, vol, (double)sigmas[s], &f);
+      const JetCodeSink ck = {dEdges + (size_t)s * IFE_NUM_FEATURES * n_edges, n_edges, code_of(s), nvox};
+      if (!r) r = launch_jet_codes(ctx, f, clamp, vol, ck);
+      if (!r) r = each_scale(s, (const uint8_t *)ck.code, (const uint8_t *)clamp);
+    }
+    return r;
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -389,6 +417,35 @@ int ife_bag_image_dense(ife_ctx *ctx, const void *image, int image_dtype, const 
   if ((rc = stage_in(ctx, mem, image, nvox * dtype_size(image_dtype), ctx->st_img, &dI))) return rc;
   const size_t cbytes = (size_t)cen.n * ncol * nb * 4;
   if ((rc = ensure(ctx, ctx->st_out, cbytes))) return rc;
+  if (ctx->differential) {
+    // the jet workspace first (outside the bound, as the finite-difference workspace is), so that
+    // the free memory is what is left; then labels and the codes of one scale (always taken), and
+    // the box passes, which find their codes in place, get the rest
+    if ((rc = jet_reserve(ctx, vol))) return rc;
+    size_t budget;
+    if ((rc = dense_budget(ctx, ctx->dn_ws.cap + ctx->dn_feat.cap, &budget))) return rc;
+    const size_t off_c = (nvox + 15) / 16 * 16, fbytes = off_c + nvox * IFE_NUM_FEATURES;
+    int cg, bg;
+    if ((rc = dense_groups(ctx, budget > fbytes ? budget - fbytes : 0, nvox, IFE_NUM_FEATURES, nb, 0, &cg, &bg)))
+      return rc;
+    const size_t planes = (size_t)cg * bg;
+    if ((rc = ensure(ctx, ctx->dn_ws, 3 * planes * nvox))) return rc;
+    const DenseOut out = {(uint32_t *)ctx->st_out.p, 0, (int64_t)ncol * nb, 1};
+    auto box_scale = [&](int s, const uint8_t *code, const uint8_t *) {
+      int r = IFE_OK;
+      for (int c0 = 0; c0 < IFE_NUM_FEATURES && !r; c0 += cg)
+        r = dense_box_passes(ctx, code + (size_t)c0 * nvox, g.nvox, std::min(cg, IFE_NUM_FEATURES - c0), g, cen.flag,
+                             cen.seg_base, ctx->dn_ws.p, planes, bg, nb, out,
+                             ((int64_t)s * IFE_NUM_FEATURES + c0) * nb);
+      return r;
+    };
+    if ((rc = dense_jet_scales(ctx, dI, image_dtype, in.mask, mask_dtype, vol, sigmas, n_sigmas, in.edges, n_edges,
+                               fbytes, [&](int) { return (uint8_t *)ctx->dn_feat.p + off_c; }, box_scale)))
+      return rc;
+    IFE_HIP(ctx, hipMemcpyAsync(counts, ctx->st_out.p, cbytes, hipMemcpyDeviceToHost, ctx->stream));
+    IFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return IFE_OK;
+  }
   // the budget: at most half for the features of a group of scales, the box counts get the rest
   size_t budget;
   if ((rc = dense_budget(ctx, ctx->dn_ws.cap + ctx->dn_feat.cap, &budget))) return rc;
@@ -503,9 +560,14 @@ int dense_stream_begin(ife_ctx *ctx, const void *image, int image_dtype, const v
     plane_rows[(size_t)o] = (o + 1 < nplanes ? (int64_t)first[(size_t)o + 1] : cen.n) - (int64_t)first[(size_t)o];
   // the budget: features of a group of scales (at most half, as in ife_bag_image_dense), the codes,
   // and of the rest an eighth per block buffer (three of them) and half for the box passes
+  // (IFE_OPT_DIFFERENTIAL: no feature share -- the labels only, behind the jet workspace, which lies
+  // outside the bound as the finite-difference workspace does)
+  const bool differential = ctx->differential != 0;
+  if (differential && (rc = jet_reserve(ctx, vol))) return rc;
   size_t budget;
   if ((rc = dense_budget(ctx, ctx->dn_feat.cap, &budget))) return rc;
-  const DenseScalePlan plan = dense_scale_plan(budget / 2, nvox, n_sigmas);
+  const DenseScalePlan plan =
+      differential ? DenseScalePlan{0, 0, (nvox + 15) / 16 * 16} : dense_scale_plan(budget / 2, nvox, n_sigmas);
   const size_t cbytes = (size_t)ncol * nvox;
   const size_t rest = budget > plan.fbytes + cbytes ? budget - plan.fbytes - cbytes : 0;
   const size_t row_bytes = (size_t)ncol * nb * 4;
@@ -536,8 +598,13 @@ int dense_stream_begin(ife_ctx *ctx, const void *image, int image_dtype, const v
                       in.edges + (size_t)s * IFE_NUM_FEATURES * n_edges, n_edges,
                       (uint8_t *)ds.codes.p + (size_t)s * IFE_NUM_FEATURES * nvox);
   };
-  if ((rc = dense_scale_loop(ctx, dI, image_dtype, in.mask, mask_dtype, vol, sigmas, n_sigmas, plan, code_scale)))
-    return rc;
+  if (differential)  // the codes straight from the jet into their place
+    rc = dense_jet_scales(ctx, dI, image_dtype, in.mask, mask_dtype, vol, sigmas, n_sigmas, in.edges, n_edges,
+                          plan.fbytes, [&](int s) { return (uint8_t *)ds.codes.p + (size_t)s * IFE_NUM_FEATURES * nvox; },
+                          [](int, const uint8_t *, const uint8_t *) { return (int)IFE_OK; });
+  else
+    rc = dense_scale_loop(ctx, dI, image_dtype, in.mask, mask_dtype, vol, sigmas, n_sigmas, plan, code_scale);
+  if (rc) return rc;
   *max_block_rows = max_rows;
   return dense_stream_count(ctx, 0);  // the first block is under way when _begin returns
 }

@@ -101,6 +101,16 @@ __global__ __launch_bounds__(256) void dense_boxes_kernel(const uint8_t *__restr
   }
 }
 
+// DenseHistogram bin of v: the lower bound over the nedges ascending edges e.
+__device__ __forceinline__ int dense_bin(const float *e, int nedges, float v) {
+  int lo = 0, hi = nedges;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (e[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
 // Bin codes of components [c0, c0 + gridDim.y) of one feature volume: code[c][i] = DenseHistogram
 // bin of the component value (lower bound over the edges; a NaN goes to bin 0 because
 // `e[mid] < v` is false throughout, as in roi_histogram_kernel), DENSE_OUTSIDE where mask == 0.
@@ -120,15 +130,7 @@ __global__ __launch_bounds__(256) void dense_code_kernel(const float *__restrict
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvox;
        i += (int64_t)gridDim.x * blockDim.x) {
     int lo = DENSE_OUTSIDE;
-    if (mask[i] != 0) {
-      const float v = f[i * vox_stride];
-      int hi = nedges;
-      lo = 0;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (e[mid] < v) lo = mid + 1; else hi = mid;
-      }
-    }
+    if (mask[i] != 0) lo = dense_bin(e, nedges, f[i * vox_stride]);
     out[i] = (uint8_t)lo;
   }
 }

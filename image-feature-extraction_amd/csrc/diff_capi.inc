@@ -1,7 +1,8 @@
 // diff_capi.inc -- the differential normalized convolution complete to second order
 // (include/ife_hip.h: ife_normalized_convolution_jet, ife_differential_features, DESIGN.md
 // section 4 "Differential features"); included at the end of ife_capi.hip (shares its context,
-// staging, line-pass and profiling helpers).
+// staging, line-pass and profiling helpers), in front of stats_capi.inc and dense_capi.inc, whose
+// composite calls come here under IFE_OPT_DIFFERENTIAL.
 //
 // Pass tree.  For f in {cT, c} and every order triple (ox, oy, oz) with ox + oy + oz <= 2 the
 // field F[ox,oy,oz](f) = RG_y^oy(RG_x^ox(RG_z^oz(f))) is built by line passes in ITK's order
@@ -152,18 +153,25 @@ int jet_check_pointers(ife_ctx *ctx, const void *in0, size_t in0_size, const voi
   return IFE_OK;
 }
 
-// The pointwise pass over the twenty fields.  mask: FEATURES8 only (may be null).
-template <int MODE, typename TM>
-int launch_jet(ife_ctx *ctx, const JetFields &f, const TM *mask, float *out, const ife_volume_desc *vol,
-               int layout) {
-  const int64_t n = vol->nx * vol->ny * vol->nz;
+// What the pointwise kernels need of the volume (pvec is launch_jet's own).
+JetGeom jet_geom(const ife_volume_desc *vol) {
   JetGeom g;
-  g.nvox = n;
+  g.nvox = vol->nx * vol->ny * vol->nz;
   const double sp[3] = {vol->sx, vol->sy, vol->sz};
   for (int a = 0; a < 3; ++a) g.r[a] = 1.0 / sp[a];
   int p = 0;
   for (int i = 0; i < 3; ++i)
     for (int j = i; j < 3; ++j) g.rr[p++] = g.r[i] * g.r[j];
+  g.pvec = 0;
+  return g;
+}
+
+// The pointwise pass over the twenty fields.  mask: FEATURES8 only (may be null).
+template <int MODE, typename TM>
+int launch_jet(ife_ctx *ctx, const JetFields &f, const TM *mask, float *out, const ife_volume_desc *vol,
+               int layout) {
+  const int64_t n = vol->nx * vol->ny * vol->nz;
+  JetGeom g = jet_geom(vol);
   g.pvec = reinterpret_cast<uintptr_t>(out) % 16 == 0 && n % 4 == 0;
   // the fields are slots of the workspace (16-byte aligned); the mask decides the vector form
   const bool vec = reinterpret_cast<uintptr_t>(mask) % (4 * sizeof(TM)) == 0;
@@ -193,6 +201,44 @@ int launch_jet(ife_ctx *ctx, const JetFields &f, const TM *mask, float *out, con
   return IFE_OK;
 }
 
+// IFE_OPT_DIFFERENTIAL: the features of the sampled voxels of one scale straight from the twenty
+// fields into eight sample columns (stats_capi.inc); one wave per 64-voxel row segment.  They share
+// the jet's row of the kernel-time table.
+int launch_jet_samples(ife_ctx *ctx, const JetFields &f, const ife_volume_desc *vol, const JetSampleSink &sk) {
+  const JetGeom g = jet_geom(vol);
+  ProfScope ps(ctx, KK_JET);
+  const unsigned blocks = (unsigned)((sk.nseg + 3) / 4);  // nseg < 2^31 (the caller's check)
+  with_const<1, 2, 0>(ctx->trig_mode, [&](auto TRIG) {
+    hipLaunchKernelGGL((jet_samples_kernel<decltype(TRIG)::value>), dim3(blocks), dim3(256), 0, ctx->stream, f, g, sk);
+  });
+  IFE_HIP(ctx, hipGetLastError());
+  return IFE_OK;
+}
+
+// IFE_OPT_DIFFERENTIAL: the eight planes of bin codes of one scale straight from the twenty fields
+// (dense_capi.inc).  mask: the clamped labels.  The 4-byte form where mask, codes and the plane
+// stride allow it, the scalar form for the rest.
+int launch_jet_codes(ife_ctx *ctx, const JetFields &f, const uint8_t *mask, const ife_volume_desc *vol,
+                     const JetCodeSink &ck) {
+  const JetGeom g = jet_geom(vol);
+  const int64_t n = g.nvox;
+  const bool vec = reinterpret_cast<uintptr_t>(mask) % 4 == 0 && reinterpret_cast<uintptr_t>(ck.code) % 4 == 0 &&
+                   ck.stride % 4 == 0;
+  const int64_t n4 = vec ? n / 4 : 0;
+  ProfScope ps(ctx, KK_JET);
+  with_const<1, 2, 0>(ctx->trig_mode, [&](auto TRIG) {
+    constexpr int T = decltype(TRIG)::value;
+    if (n4 > 0)
+      hipLaunchKernelGGL((jet_codes_kernel_vec4<T>), dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, ctx->stream, f,
+                         mask, g, ck, n4);
+    if (n4 * 4 < n)
+      hipLaunchKernelGGL((jet_codes_kernel_scalar<T>), dim3((unsigned)((n - n4 * 4 + 255) / 256)), dim3(256), 0,
+                         ctx->stream, f, mask, g, ck, n4 * 4, n);
+  });
+  IFE_HIP(ctx, hipGetLastError());
+  return IFE_OK;
+}
+
 // cT = float(image) * float(mask) and c = float(mask) into ife_ctx::pre (c = 1 without a mask)
 template <typename TI, typename TM>
 int jet_sources(ife_ctx *ctx, const TI *img, const TM *msk, int64_t n) {
@@ -210,6 +256,45 @@ int jet_sources(ife_ctx *ctx, const TI *img, const TM *msk, int64_t n) {
     IFE_HIP(ctx, hipGetLastError());
   }
   return IFE_OK;
+}
+
+// Everything jet_sources and jet_fields allocate for this volume, now: a caller that sizes a budget
+// from the free device memory does so behind it.
+int jet_reserve(ife_ctx *ctx, const ife_volume_desc *vol) {
+  const size_t pitch = ((size_t)(vol->nx * vol->ny * vol->nz) + 3) / 4 * 4;
+  int rc = ensure(ctx, ctx->pre[0], pitch * sizeof(float));
+  if (!rc) rc = ensure(ctx, ctx->pre[1], pitch * sizeof(float));
+  if (!rc) rc = ensure(ctx, ctx->dj_ws, (size_t)JET_SLOTS * pitch * sizeof(float));
+  if (!rc) rc = ensure_ck(ctx, vol, IIR_MAX_JOBS);
+  return rc;
+}
+
+// Every scale of ife_differential_features into dout (device), one after the other; records an
+// event behind each scale into ctx->scale_events when that is set (the scale stream).
+template <typename TI, typename TM>
+int differential_typed(ife_ctx *ctx, const TI *img, const TM *msk, const ife_volume_desc *vol, const float *sigmas,
+                       int n_sigmas, float *dout, int layout) {
+  const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
+  int r = jet_sources(ctx, img, msk, (int64_t)n);
+  for (int s = 0; s < n_sigmas && !r; ++s) {  // one scale after the other over the same workspace
+    JetFields f;
+    r = jet_fields(ctx, (const float *)ctx->pre[0].p, (const float *)ctx->pre[1].p, vol, (double)sigmas[s], &f);
+    if (!r) r = launch_jet<JET_FEATURES8>(ctx, f, msk, dout + (size_t)s * n * IFE_NUM_FEATURES, vol, layout);
+    if (!r && ctx->scale_events) {
+      hipEvent_t e;
+      IFE_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      ctx->scale_events->push_back(e);
+      IFE_HIP(ctx, hipEventRecord(e, ctx->stream));
+    }
+  }
+  return r;
+}
+
+int differential_scales(ife_ctx *ctx, const void *dI, int image_dtype, const void *dM, int mask_dtype,
+                        const ife_volume_desc *vol, const float *sigmas, int n_sigmas, float *dout, int layout) {
+  return with_types(image_dtype, dI, dM != nullptr, mask_dtype, dM, [&](auto img, auto msk) {
+    return differential_typed(ctx, img, msk, vol, sigmas, n_sigmas, dout, layout);
+  });
 }
 
 }  // namespace
@@ -260,13 +345,7 @@ int ife_differential_features(ife_ctx *ctx, const void *image, int image_dtype, 
                                layout)))
     return rc;
   rc = with_types(image_dtype, dI, mask != nullptr, mask_dtype, dM, [&](auto img, auto msk) {
-    int r = jet_sources(ctx, img, msk, (int64_t)n);
-    for (int s = 0; s < n_sigmas && !r; ++s) {  // one scale after the other over the same workspace
-      JetFields f;
-      r = jet_fields(ctx, (const float *)ctx->pre[0].p, (const float *)ctx->pre[1].p, vol, (double)sigmas[s], &f);
-      if (!r) r = launch_jet<JET_FEATURES8>(ctx, f, msk, (float *)dO + (size_t)s * scale_floats, vol, layout);
-    }
-    return r;
+    return differential_typed(ctx, img, msk, vol, sigmas, n_sigmas, (float *)dO, layout);
   });
   if (rc) return rc;
   return stage_out_end(ctx, mem, out, out_bytes);

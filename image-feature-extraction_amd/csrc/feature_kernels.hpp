@@ -25,6 +25,7 @@
 #include <float.h>
 #include <stdint.h>
 
+#include "dense_kernels.hpp"
 #include "eigen_device.hpp"
 
 namespace ife {
@@ -1054,6 +1055,144 @@ __global__ __launch_bounds__(256) void jet_kernel_scalar(JetFields f, const TM *
       else out[i * NOUT + k] = v;
     }
   }
+}
+
+// ---- the jet straight into the consumers' formats (IFE_OPT_DIFFERENTIAL) ----
+// Both kernels below run jet_point<JET_FEATURES8, TRIG> unchanged and apply the masking rule of
+// jet_kernel_*, so every value is the one ife_differential_features stores for that voxel; what
+// they leave out is the feature volume between the jet and its consumer.  Their grids are not
+// capped: one wave per row segment, one lane per piece or voxel.
+
+// Differential counterpart of FEAT_SAMPLES8: the eight features of every sampled voxel go to eight
+// sample columns, compacted in raster order.  code (sample_code_kernel): bit 0 = sample here, bit
+// 1 = label non-zero (the values are 0 where it is clear); seg_base: exclusive scan of the sample
+// counts of the 64-voxel row segments s = bx + gx * (y + ny * z).
+struct JetSampleSink {
+  const uint8_t *code;
+  const uint32_t *seg_base;
+  float *columns;          // column k at columns + k * stride
+  int64_t stride, offset;  // elements between columns, samples already in them
+  int nx, gx;
+  int64_t nseg;
+};
+// One wave per row segment, lanes along x.  A wave without a sample returns before any load.
+template <int TRIG>
+__global__ __launch_bounds__(256) void jet_samples_kernel(JetFields f, JetGeom g, JetSampleSink sk) {
+  const int lane = threadIdx.x & 63;
+  const int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (s >= sk.nseg) return;  // whole waves
+  const int64_t row = s / sk.gx;
+  const int x = (int)(s % sk.gx) * 64 + lane;
+  // lanes behind the row's end read its last voxel and store nothing
+  const int64_t i = row * sk.nx + min(x, sk.nx - 1);
+  const int c = x < sk.nx ? (int)sk.code[i] : 0;
+  const bool samp = (c & 1) != 0, keep = (c & 3) == 3;
+  const uint64_t sm = __builtin_amdgcn_ballot_w64(samp);
+  if (sm == 0) return;
+  float o[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) o[k] = 0.0f;
+  if (__builtin_amdgcn_ballot_w64(keep) != 0) {
+    float N[10], D[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      N[k] = __builtin_nontemporal_load(f.n[k] + i);
+      D[k] = __builtin_nontemporal_load(f.d[k] + i);
+    }
+    jet_point<JET_FEATURES8, TRIG>(N, D, g, o);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = keep ? o[k] : 0.0f;
+  }
+  if (samp) {
+    float *q = sk.columns + sk.offset + (int64_t)sk.seg_base[s] + lanes_below(sm);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) q[(int64_t)k * sk.stride] = o[k];
+  }
+}
+
+// Differential counterpart of the feature kernel followed by dense_code_kernel: eight planes of
+// one-byte bin codes, code[k * stride + voxel] = dense_bin of feature k over edges[k][0 .. nedges)
+// (a NaN goes to bin 0 as there), DENSE_OUTSIDE where mask == 0.  mask: the labels clamped to
+// {0, 1}.  The edges of the eight components stand in LDS (8 * nedges floats).
+struct JetCodeSink {
+  const float *edges;  // [8][nedges], device
+  int nedges;
+  uint8_t *code;
+  int64_t stride;  // bytes between the component planes
+};
+__device__ __forceinline__ void jet_codes_edges(const JetCodeSink &ck, float *e) {
+  for (int t = threadIdx.x; t < 8 * ck.nedges; t += blockDim.x) e[t] = ck.edges[t];
+  __syncthreads();
+}
+// Pieces [0, n4) of four consecutive voxels, one per lane: a 16-byte load per field, four mask
+// bytes in one load, one 4-byte store per component.  Needs 16-byte aligned fields, and mask,
+// code and stride aligned to 4 bytes (the host sends everything else through the scalar form).
+template <int TRIG>
+__global__ __launch_bounds__(256) void jet_codes_kernel_vec4(JetFields f, const uint8_t *__restrict__ mask,
+                                                             JetGeom g, JetCodeSink ck, int64_t n4) {
+  __shared__ float e[8 * DENSE_MAX_EDGES];
+  jet_codes_edges(ck, e);
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  const uint32_t m = reinterpret_cast<const uint32_t *>(mask)[i];
+  uint32_t pk[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) pk[k] = 0u;
+  // a wave outside the mask loads no field
+  if (__builtin_amdgcn_ballot_w64(m != 0u) == 0) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) pk[k] = 0x01010101u * (uint32_t)DENSE_OUTSIDE;
+  } else {
+    f32x4 vn[10], vd[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      vn[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(f.n[k]) + i);
+      vd[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(f.d[k]) + i);
+    }
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const bool keep = ((m >> (8 * v)) & 0xffu) != 0u;
+      int b[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) b[k] = DENSE_OUTSIDE;
+      if (__builtin_amdgcn_ballot_w64(keep) != 0) {
+        float N[10], D[10], o[8];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) { N[k] = vn[k][v]; D[k] = vd[k][v]; }
+        jet_point<JET_FEATURES8, TRIG>(N, D, g, o);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) b[k] = keep ? dense_bin(e + k * ck.nedges, ck.nedges, o[k]) : DENSE_OUTSIDE;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) pk[k] |= (uint32_t)b[k] << (8 * v);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) reinterpret_cast<uint32_t *>(ck.code + (int64_t)k * ck.stride)[i] = pk[k];
+}
+// Voxels [i0, i1) one per lane: the tail behind the last whole piece, and everything where an
+// address rules the 4-byte form out.
+template <int TRIG>
+__global__ __launch_bounds__(256) void jet_codes_kernel_scalar(JetFields f, const uint8_t *__restrict__ mask,
+                                                               JetGeom g, JetCodeSink ck, int64_t i0, int64_t i1) {
+  __shared__ float e[8 * DENSE_MAX_EDGES];
+  jet_codes_edges(ck, e);
+  const int64_t i = i0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= i1) return;
+  const bool keep = mask[i] != 0;
+  int b[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) b[k] = DENSE_OUTSIDE;
+  if (__builtin_amdgcn_ballot_w64(keep) != 0) {
+    float N[10], D[10], o[8];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) { N[k] = f.n[k][i]; D[k] = f.d[k][i]; }
+    jet_point<JET_FEATURES8, TRIG>(N, D, g, o);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) b[k] = keep ? dense_bin(e + k * ck.nedges, ck.nedges, o[k]) : DENSE_OUTSIDE;
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) ck.code[(int64_t)k * ck.stride + i] = (uint8_t)b[k];
 }
 
 }  // namespace ife

@@ -153,6 +153,7 @@ struct ife_ctx {
   int const_lines = 1;   // lines of one repeated 0 or 1 are copied, not filtered, where verified exact
   int feat_ring = 1;     // feature kernel: planes by LDS-DMA into a ring where the source is one float field
   int z_sweep = 1;       // first axis pass: one causal sweep for all scales from image and mask, no prepass
+  int differential = 0;  // IFE_OPT_DIFFERENTIAL: the composite calls take their features from the jet
   std::map<std::tuple<double, double, int64_t>, uint32_t> const_flags;  // (sigma, spacing, length) -> IirJob::const_lines
   // per scale slot: numerator ping/pong, denominator ping/pong (up to three scales run
   // through the line kernels together)
@@ -202,6 +203,9 @@ struct ife_ctx {
 namespace {
 
 void dense_stream_release(ife_ctx *ctx);  // dense_capi.inc
+// diff_capi.inc: every scale of ife_differential_features from device inputs into dout (device)
+int differential_scales(ife_ctx *ctx, const void *dI, int image_dtype, const void *dM, int mask_dtype,
+                        const ife_volume_desc *vol, const float *sigmas, int n_sigmas, float *dout, int layout);
 
 int fail(ife_ctx *ctx, int code, const char *fmt, ...) {
   char buf[512];
@@ -1057,13 +1061,14 @@ static int emphysema_check(ife_ctx *ctx, const void *image, int image_dtype, con
   return check_mask_dtype(ctx, mask, mask_dtype, true);
 }
 
-// Stage image and mask (HOST mode), then every scale into dout (device).  With `uploaded`, an
+// Stage image and mask (HOST mode), then every scale into dout (device), by finite differences or
+// (`differential`) from the jet.  With `uploaded`, an
 // event is recorded behind the uploads and handed to the caller, who waits for it: from
 // page-locked memory the uploads run asynchronously to the host.  *uploaded stays null when this
 // stopped before the scales.
 static int emphysema_staged(ife_ctx *ctx, int mem, const void *image, int image_dtype, const void *mask,
                             int mask_dtype, const ife_volume_desc *vol, const float *sigmas, int n_sigmas,
-                            float *dout, int layout, hipEvent_t *uploaded = nullptr) {
+                            float *dout, int layout, hipEvent_t *uploaded = nullptr, bool differential = false) {
   const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
   const void *dI, *dM;
   int rc;
@@ -1082,6 +1087,8 @@ static int emphysema_staged(ife_ctx *ctx, int mem, const void *image, int image_
     }
     *uploaded = e;
   }
+  if (differential)  // IFE_OPT_DIFFERENTIAL in the scale stream: the scales of ife_differential_features
+    return differential_scales(ctx, dI, image_dtype, dM, mask_dtype, vol, sigmas, n_sigmas, dout, layout);
   return with_types(image_dtype, dI, mask != nullptr, mask_dtype, dM, [&](auto img, auto msk) {
     return emphysema_typed(ctx, img, msk, vol, sigmas, n_sigmas, dout, layout);
   });
@@ -1178,6 +1185,10 @@ int ife_ctx_set_option(ife_ctx *ctx, int option, int value) {
       return IFE_OK;
     case IFE_OPT_Z_SWEEP:
       ctx->z_sweep = value ? 1 : 0;
+      return IFE_OK;
+    case IFE_OPT_DIFFERENTIAL:
+      if (value != 0 && value != 1) return fail(ctx, IFE_E_ARG, "the differential option must be 0 or 1");
+      ctx->differential = value;
       return IFE_OK;
     case IFE_OPT_DENSE_SCRATCH_MB:
       if (value < 0) return fail(ctx, IFE_E_ARG, "the dense scratch bound must be >= 0 MiB");
@@ -1395,7 +1406,9 @@ int ife_emphysema_features_begin(ife_ctx *ctx, const void *image, int image_dtyp
                             IFE_MEM_HOST)))
     return rc;
   if ((rc = ife_emphysema_features_end(ctx))) return rc;  // drop an earlier, unfinished run
-  if ((rc = ife_ctx_reserve(ctx, vol))) return rc;
+  // the option as it stands now decides for the whole stream: _fetch only copies what is enqueued here
+  const bool differential = ctx->differential != 0;
+  if (!differential && (rc = ife_ctx_reserve(ctx, vol))) return rc;
   ctx->sc_scale_bytes = (size_t)(vol->nx * vol->ny * vol->nz) * IFE_NUM_FEATURES * sizeof(float);
   if ((rc = ensure(ctx, ctx->sc_out, ctx->sc_scale_bytes * (size_t)n_sigmas))) return rc;
   if (!ctx->sc_copy) IFE_HIP(ctx, hipStreamCreateWithFlags(&ctx->sc_copy, hipStreamNonBlocking));
@@ -1404,7 +1417,7 @@ int ife_emphysema_features_begin(ife_ctx *ctx, const void *image, int image_dtyp
   hipEvent_t uploaded = nullptr;
   ctx->scale_events = &ctx->sc_done;
   rc = emphysema_staged(ctx, IFE_MEM_HOST, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas,
-                        (float *)ctx->sc_out.p, layout, &uploaded);
+                        (float *)ctx->sc_out.p, layout, &uploaded, differential);
   ctx->scale_events = nullptr;
   if (!uploaded) return rc;  // stopped before the scales
   const hipError_t up = hipEventSynchronize(uploaded);
@@ -1695,8 +1708,8 @@ int ife_reset_kernel_times(ife_ctx *ctx) {
 
 }  // extern "C"
 
+#include "diff_capi.inc"  // before its users: the sample and dense calls under IFE_OPT_DIFFERENTIAL
 #include "stats_capi.inc"
 #include "distance_capi.inc"
 #include "dense_capi.inc"
-#include "diff_capi.inc"
 #include "multi_capi.inc"

@@ -184,6 +184,8 @@ const char *ife_multi_last_error(const ife_multi *m) { return m ? m->err.c_str()
 
 int ife_multi_set_option(ife_multi *m, int option, int value) {
   if (!m) return IFE_E_ARG;
+  if (option == IFE_OPT_DIFFERENTIAL && value == 1)
+    return mfail(m, IFE_E_ARG, "the differential path runs on one device (IFE_OPT_DIFFERENTIAL stays 0 here)");
   for (auto &R : m->ranks) {
     IFE_MCTX(m, R, R.bulk, ife_ctx_set_option(R.bulk, option, value));
     IFE_MCTX(m, R, R.chain, ife_ctx_set_option(R.chain, option, value));

@@ -24,13 +24,15 @@
 // differentiated, not the result, so nothing is read where the normalized convolution is an
 // extrapolation) instead of finite differences of the smoothed value.  The environment variable
 // IFE_DIFFERENTIAL sets the initial value (unset or 0: off), because the tools keep the
-// reference's flags.  Every Update() is then one self-contained call for the current sigma (no
-// begin/fetch streaming); with several devices (IFE_DEVICES) it throws.
+// reference's flags.  The switch is the context option IFE_OPT_DIFFERENTIAL, set around this
+// filter's own calls and put back to the environment's value afterwards (ife::host::Engine sets
+// that one for every tool), so announced scales stream through begin/fetch on this path as on the
+// default one; without them every Update() is one self-contained call.  With several devices
+// (IFE_DEVICES) it throws.
 #ifndef __ImageToEmphysemaFeaturesFilter_h
 #define __ImageToEmphysemaFeaturesFilter_h
 
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "ife/Host/Engine.h"
@@ -81,20 +83,9 @@ class ImageToEmphysemaFeaturesFilter {
     int which = -1;
     for (size_t k = 0; k < scales_.size(); ++k)
       if (scales_[k] == (float)sigma_) { which = (int)k; break; }
-    if (differential_) {
-      if (e.multi())
-        throw ExceptionObject("the differential convolution runs on one device; unset IFE_DEVICES",
-                              "ImageToEmphysemaFeaturesFilter");
-      const float sig = (float)sigma_;
-      e.check(ife_differential_features(
-                  e.ctx(), image_->GetBufferPointer(), ife::host::ImageDType<PixelType>::value,
-                  mask_->GetBufferPointer(),
-                  ife::host::MaskDType<typename InputMaskType::PixelType>::value, &d, &sig, 1,
-                  out_->GetBufferPointer(), IFE_INTERLEAVED, IFE_MEM_HOST),
-              "ImageToEmphysemaFeaturesFilter");
-      dirty_ = false;
-      return;
-    }
+    if (differential_ && e.multi())
+      throw ExceptionObject("the differential convolution runs on one device; unset IFE_DEVICES",
+                            "ImageToEmphysemaFeaturesFilter");
     if (ife_multi *multi = e.multi()) {  // IFE_DEVICES: Z-slabs over several devices
       const int idt = ife::host::ImageDType<PixelType>::value;
       const int mdt = ife::host::MaskDType<typename InputMaskType::PixelType>::value;
@@ -117,6 +108,14 @@ class ImageToEmphysemaFeaturesFilter {
       dirty_ = false;
       return;
     }
+    // the filter's switch is the context's option while its own calls run (_begin reads it)
+    struct OptionScope {
+      ife_ctx *c;
+      OptionScope(ife_ctx *ctx, bool on) : c(ctx) { (void)ife_ctx_set_option(c, IFE_OPT_DIFFERENTIAL, on ? 1 : 0); }
+      ~OptionScope() {
+        (void)ife_ctx_set_option(c, IFE_OPT_DIFFERENTIAL, ife::host::Engine::DifferentialFromEnvironment() ? 1 : 0);
+      }
+    } scope(e.ctx(), differential_);
     if (which >= 0) {  // the announced schedule: everything is started once, fetched per scale
       if (!streaming_) {
         e.check(ife_emphysema_features_begin(
@@ -133,7 +132,7 @@ class ImageToEmphysemaFeaturesFilter {
       return;
     }
     const float sig = (float)sigma_;
-    e.check(ife_emphysema_features(
+    e.check((differential_ ? ife_differential_features : ife_emphysema_features)(
                 e.ctx(), image_->GetBufferPointer(), ife::host::ImageDType<PixelType>::value,
                 mask_->GetBufferPointer(),
                 ife::host::MaskDType<typename InputMaskType::PixelType>::value, &d, &sig, 1,
@@ -162,11 +161,7 @@ class ImageToEmphysemaFeaturesFilter {
   const InputMaskType *mask_ = nullptr;
   ScalarRealType sigma_ = 1.0;  // .hxx:18
   bool dirty_ = true;
-  bool differential_ = DifferentialFromEnvironment();
-  static bool DifferentialFromEnvironment() {
-    const char *v = std::getenv("IFE_DIFFERENTIAL");
-    return v && v[0] && std::strcmp(v, "0") != 0;
-  }
+  bool differential_ = ife::host::Engine::DifferentialFromEnvironment();
   typename OutputImageType::Pointer out_;
 };
 

@@ -6,6 +6,7 @@
 #define IFE_HOST_ENGINE_H
 
 #include <cstdlib>
+#include <cstring>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -25,13 +26,36 @@ class Engine {
   }
   ife_ctx *ctx() {
     if (!ctx_) {
+      // IFE_DIFFERENTIAL (unset, empty or "0": off): every tool takes its features from the
+      // differential normalized convolution (IFE_OPT_DIFFERENTIAL), because the tools keep the
+      // reference's flags.  One device only.
+      const bool differential = DifferentialFromEnvironment();
+      if (differential && devices().size() > 1)
+        throw itk::ExceptionObject("the differential convolution runs on one device; unset IFE_DEVICES",
+                                   "ife::host::Engine");
       const char *d = std::getenv("IFE_DEVICE");
       const int rc = ife_ctx_create(d ? std::atoi(d) : 0, &ctx_);
       if (rc != IFE_OK) throw itk::ExceptionObject(ife_last_error(nullptr), "ife::host::Engine");
       if (const char *t = std::getenv("IFE_TRIG_MODE")) ife_ctx_set_option(ctx_, IFE_OPT_TRIG_MODE, std::atoi(t));
       if (const char *t = std::getenv("IFE_DSCALE_MODE")) ife_ctx_set_option(ctx_, IFE_OPT_DSCALE_MODE, std::atoi(t));
+      if (differential) check(ife_ctx_set_option(ctx_, IFE_OPT_DIFFERENTIAL, 1), "ife::host::Engine");
     }
     return ctx_;
+  }
+  static bool DifferentialFromEnvironment() {
+    const char *v = std::getenv("IFE_DIFFERENTIAL");
+    return v && v[0] && std::strcmp(v, "0") != 0;
+  }
+  // the entries of IFE_DEVICES
+  static std::vector<int> devices() {
+    std::vector<int> devs;
+    if (const char *d = std::getenv("IFE_DEVICES")) {
+      std::stringstream ss(d);
+      std::string tok;
+      while (std::getline(ss, tok, ','))
+        if (!tok.empty()) devs.push_back(std::atoi(tok.c_str()));
+    }
+    return devs;
   }
   void check(int rc, const char *where) {
     if (rc != IFE_OK) throw itk::ExceptionObject(ife_last_error(ctx_), where);
@@ -41,13 +65,7 @@ class Engine {
   ife_multi *multi() {
     if (!multi_tried_) {
       multi_tried_ = true;
-      std::vector<int> devs;
-      if (const char *d = std::getenv("IFE_DEVICES")) {
-        std::stringstream ss(d);
-        std::string tok;
-        while (std::getline(ss, tok, ','))
-          if (!tok.empty()) devs.push_back(std::atoi(tok.c_str()));
-      }
+      const std::vector<int> devs = devices();
       if (devs.size() > 1) {
         if (ife_multi_create(devs.data(), (int)devs.size(), &multi_) != IFE_OK)
           throw itk::ExceptionObject(ife_multi_last_error(nullptr), "ife::host::Engine");

@@ -118,7 +118,26 @@ typedef enum {
    * kernel proper then makes backward sweeps only.  In force with IFE_OPT_IIR_CKPT 2.  0: the
    * prepass, and every (scale, field) job sweeps forward on its own.  Same results bit for
    * bit. */
-  IFE_OPT_Z_SWEEP = 12
+  IFE_OPT_Z_SWEEP = 12,
+  /* 0 (default) or 1 (anything else: IFE_E_ARG): the feature path the COMPOSITE calls run
+   * internally.  With 1, ife_samples_add_image, ife_bag_image, ife_bag_image_dense,
+   * ife_bag_dense_stream_begin (and so _next) and ife_emphysema_features_begin / _fetch / _end
+   * give bit for bit what their documented composition gives when ife_differential_features
+   * stands in for ife_emphysema_features: the same mask handed over (labels clamped to {0,1} in
+   * the bag and sample calls, the caller's mask in the scale stream), the context's trig mode,
+   * the same component order and masking rule (mask != 0 ? v : 0).  The sample columns and the
+   * dense bin codes are then written straight from the jet (csrc/feature_kernels.hpp:
+   * jet_samples_kernel, jet_codes_kernel_*): no feature volume exists in the all-foreground
+   * sample branch or in the dense calls, whose budget has no feature share (the jet workspace,
+   * 140 bytes per voxel, lies outside IFE_OPT_DENSE_SCRATCH_MB as the finite-difference
+   * workspace does).  A stream takes the value in force at its _begin; setting the option
+   * between _begin and _fetch / _next changes nothing of what that stream delivers.
+   * ife_emphysema_features, ife_differential_features, the jet and every ife_stage_* call name
+   * their arithmetic and ignore the option.  The differential path runs on one device:
+   * ife_multi_set_option refuses the value 1.  With 0 every call does exactly what it did
+   * before the option existed.  The library reads no environment variable for it (the host
+   * Engine maps IFE_DIFFERENTIAL onto it). */
+  IFE_OPT_DIFFERENTIAL = 13
 } ife_option;
 
 typedef struct {
@@ -261,7 +280,9 @@ int ife_differential_features(ife_ctx *ctx, const void *image, int image_dtype, 
  * device copy (also done by the next _begin and by ife_ctx_destroy).  IFE_E_STATE when a
  * scale is fetched that _begin did not start.  _begin returns once image and mask have been
  * copied to the device (the scales are still running): the caller may overwrite or free them
- * from then on, page-locked memory included; `out` must stay valid until its _fetch returns. */
+ * from then on, page-locked memory included; `out` must stay valid until its _fetch returns.
+ * With IFE_OPT_DIFFERENTIAL at 1 when _begin is called, every scale is that of
+ * ife_differential_features (the value at _begin decides for the whole stream). */
 int ife_emphysema_features_begin(ife_ctx *ctx, const void *image, int image_dtype,
                                  const void *mask, int mask_dtype, const ife_volume_desc *vol,
                                  const float *sigmas, int n_sigmas, int layout);
@@ -399,7 +420,8 @@ typedef struct ife_multi ife_multi;
 int ife_multi_create(const int *devices, int n_devices, ife_multi **out);
 void ife_multi_destroy(ife_multi *m);
 const char *ife_multi_last_error(const ife_multi *m);
-/* ife_ctx_set_option on every context of the engine */
+/* ife_ctx_set_option on every context of the engine.  IFE_OPT_DIFFERENTIAL 1 is IFE_E_ARG: the
+ * differential path runs on one device (0 is accepted). */
 int ife_multi_set_option(ife_multi *m, int option, int value);
 int ife_multi_emphysema_features(ife_multi *m, const void *image, int image_dtype,
                                  const void *mask, int mask_dtype, const ife_volume_desc *vol,
@@ -456,7 +478,8 @@ int ife_roi_histograms(ife_ctx *ctx, const float *features, int layout, int ncom
 /* One image of MakeBag: labels clamped to {0,1} (:236-244), a5 at every scale with the
  * features left in HBM, then the rows above per scale.  rois, edges ([n_sigmas*8][n_edges],
  * the rows of the histogram specification) and counts
- * ([n_rois][n_sigmas*8][n_edges+1]) are HOST arrays; mem describes image and mask. */
+ * ([n_rois][n_sigmas*8][n_edges+1]) are HOST arrays; mem describes image and mask.
+ * IFE_OPT_DIFFERENTIAL 1: ife_differential_features in place of a5. */
 int ife_bag_image(ife_ctx *ctx, const void *image, int image_dtype, const void *mask,
                   int mask_dtype, const ife_volume_desc *vol, const float *sigmas, int n_sigmas,
                   const int64_t *rois, int n_rois, const float *edges, int n_edges,
@@ -500,7 +523,8 @@ int ife_dense_roi_histograms(ife_ctx *ctx, const float *features, int layout, in
 /* One image of MakeBagDense: ife_bag_image with the dense rule in place of the box list (labels
  * clamped to {0,1}, a5 at every scale, the rows above per scale).  edges and counts are HOST
  * arrays laid out as in ife_bag_image ([n_rois][n_sigmas*8][n_edges+1]); mem describes image,
- * mask and gen_mask.  Limits as for ife_dense_roi_histograms. */
+ * mask and gen_mask.  Limits as for ife_dense_roi_histograms.  IFE_OPT_DIFFERENTIAL 1: the bin
+ * codes of ife_differential_features, formed from the jet without a feature volume. */
 int ife_bag_image_dense(ife_ctx *ctx, const void *image, int image_dtype, const void *mask,
                         int mask_dtype, const void *gen_mask, int gen_mask_dtype,
                         const ife_volume_desc *vol, const float *sigmas, int n_sigmas,
@@ -540,7 +564,9 @@ int ife_bag_image_dense(ife_ctx *ctx, const void *image, int image_dtype, const 
  * The stream owns every buffer it uses between the calls, so any other call on the context is
  * legal between _begin and _end and does not change what the stream delivers.  Device memory:
  * the codes (nvox * n_sigmas*8 bytes), three block buffers (one planar that the counting fills,
- * two row-major on their way out) and the scratch of the box passes of one block. */
+ * two row-major on their way out) and the scratch of the box passes of one block.
+ * IFE_OPT_DIFFERENTIAL 1 at _begin: the codes are those of ife_differential_features, formed from
+ * the jet without a feature volume (the budget then has no feature share). */
 typedef enum { IFE_BAG_COUNTS = 0, IFE_BAG_FREQUENCIES = 1 } ife_bag_values;
 int ife_bag_dense_stream_begin(ife_ctx *ctx, const void *image, int image_dtype, const void *mask,
                                int mask_dtype, const void *gen_mask, int gen_mask_dtype,
@@ -577,7 +603,9 @@ int ife_samples_add_features(ife_ctx *ctx, ife_samples *s, int first_column,
  * columns [8i, 8i+8) -- in the all-foreground branch straight from the feature kernel (no
  * feature volume is stored), in the sampled branch from a feature volume left in HBM.  The samples object must have
  * 8*n_sigmas columns.  indices, when given, holds n_sigmas * n_indices_per_scale voxel
- * indices, scale-major. */
+ * indices, scale-major.  IFE_OPT_DIFFERENTIAL 1: both branches take the features of
+ * ife_differential_features (the all-foreground one straight from the jet, again without a
+ * feature volume). */
 int ife_samples_add_image(ife_ctx *ctx, ife_samples *s, const void *image, int image_dtype,
                           const void *mask, int mask_dtype, const ife_volume_desc *vol,
                           const float *sigmas, int n_sigmas, const uint32_t *foreground,
