@@ -258,8 +258,7 @@ int dense_scale_loop(ife_ctx *ctx, const void *dI, int image_dtype, const void *
   if ((rc = launch_clamp01(ctx, dM, mask_dtype, clamp, (int64_t)nvox))) return rc;
   for (int s0 = 0; s0 < n_sigmas; s0 += plan.sg) {
     const int ns = std::min(plan.sg, n_sigmas - s0);
-    if ((rc = ife_emphysema_features(ctx, dI, image_dtype, clamp, IFE_U8, vol, sigmas + s0, ns, feat, IFE_PLANAR,
-                                     IFE_MEM_DEVICE)))
+    if ((rc = feature_volumes(ctx, dI, image_dtype, clamp, IFE_U8, vol, sigmas + s0, ns, feat, IFE_PLANAR, false)))
       return rc;
     for (int i = 0; i < ns; ++i)
       if ((rc = each_scale(s0 + i, feat + (size_t)i * nvox * IFE_NUM_FEATURES, clamp))) return rc;
@@ -268,30 +267,20 @@ int dense_scale_loop(ife_ctx *ctx, const void *dI, int image_dtype, const void *
 }
 
 // IFE_OPT_DIFFERENTIAL: no feature volume.  The clamped labels stand at the start of dn_feat
-// (`fbytes` of it are ensured: the caller may keep more behind them); per scale the twenty fields of
-// the jet, then the eight code planes straight from them to code_of(scale) ([8][nvox] bytes), then
-// each_scale(scale, those planes, the clamped labels).  dEdges: [n_sigmas * 8][n_edges], device.
+// (`fbytes` of it are ensured: the caller may keep more behind them); the scale loop hands the
+// twenty fields of every scale to a CodeSink (scales_capi.inc) with the caller's code_of and
+// each_scale.  dEdges: [n_sigmas * 8][n_edges], device.
 template <typename C, typename F>
-int dense_jet_scales(ife_ctx *ctx, const void *dI, int image_dtype, const void *dM, int mask_dtype,
-                     const ife_volume_desc *vol, const float *sigmas, int n_sigmas, const float *dEdges, int n_edges,
-                     size_t fbytes, C &&code_of, F &&each_scale) {
-  const int64_t nvox = vol->nx * vol->ny * vol->nz;
+int dense_code_scales(ife_ctx *ctx, const void *dI, int image_dtype, const void *dM, int mask_dtype,
+                      const ife_volume_desc *vol, const float *sigmas, int n_sigmas, const float *dEdges, int n_edges,
+                      size_t fbytes, C code_of, F each_scale) {
   int rc = ensure(ctx, ctx->dn_feat, fbytes);
   if (rc) return rc;
   uint8_t *clamp = (uint8_t *)ctx->dn_feat.p;
-  if ((rc = launch_clamp01(ctx, dM, mask_dtype, clamp, nvox))) return rc;
-  if (reinterpret_cast<uintptr_t>(dI) % dtype_size(image_dtype))
-    return fail(ctx, IFE_E_ARG, "input pointers must be aligned to their element size");
+  if ((rc = launch_clamp01(ctx, dM, mask_dtype, clamp, vol->nx * vol->ny * vol->nz))) return rc;
   return with_types(image_dtype, dI, true, IFE_U8, clamp, [&](auto img, auto cm) {
-    int r = jet_sources(ctx, img, cm, nvox);
-    for (int s = 0; s < n_sigmas && !r; ++s) {
-      JetFields f;
-      r = jet_fields(ctx, (const float *)ctx->pre[0].p, (const float *)ctx->pre[1].p, vol, (double)sigmas[s], &f);
-      const JetCodeSink ck = {dEdges + (size_t)s * IFE_NUM_FEATURES * n_edges, n_edges, code_of(s), nvox};
-      if (!r) r = launch_jet_codes(ctx, f, clamp, vol, ck);
-      if (!r) r = each_scale(s, (const uint8_t *)ck.code, (const uint8_t *)clamp);
-    }
-    return r;
+    return feature_scales(ctx, img, cm, vol, sigmas, n_sigmas, true,
+                          CodeSink<C, F>{clamp, dEdges, n_edges, code_of, each_scale}, nullptr);
   });
 }
 
@@ -417,13 +406,15 @@ int ife_bag_image_dense(ife_ctx *ctx, const void *image, int image_dtype, const 
   if ((rc = stage_in(ctx, mem, image, nvox * dtype_size(image_dtype), ctx->st_img, &dI))) return rc;
   const size_t cbytes = (size_t)cen.n * ncol * nb * 4;
   if ((rc = ensure(ctx, ctx->st_out, cbytes))) return rc;
-  if (ctx->differential) {
-    // the jet workspace first (outside the bound, as the finite-difference workspace is), so that
-    // the free memory is what is left; then labels and the codes of one scale (always taken), and
-    // the box passes, which find their codes in place, get the rest
-    if ((rc = jet_reserve(ctx, vol))) return rc;
-    size_t budget;
-    if ((rc = dense_budget(ctx, ctx->dn_ws.cap + ctx->dn_feat.cap, &budget))) return rc;
+  // IFE_OPT_DIFFERENTIAL: the jet workspace first (outside the bound, as the finite-difference
+  // workspace is, which the feature call grows), so that the free memory is what is left
+  const bool differential = ctx->differential != 0;
+  if (differential && (rc = reserve_scales(ctx, vol, true))) return rc;
+  size_t budget;
+  if ((rc = dense_budget(ctx, ctx->dn_ws.cap + ctx->dn_feat.cap, &budget))) return rc;
+  if (differential) {
+    // labels and the codes of one scale (always taken), and the box passes, which find their codes
+    // in place, get the rest
     const size_t off_c = (nvox + 15) / 16 * 16, fbytes = off_c + nvox * IFE_NUM_FEATURES;
     int cg, bg;
     if ((rc = dense_groups(ctx, budget > fbytes ? budget - fbytes : 0, nvox, IFE_NUM_FEATURES, nb, 0, &cg, &bg)))
@@ -439,25 +430,20 @@ int ife_bag_image_dense(ife_ctx *ctx, const void *image, int image_dtype, const 
                              ((int64_t)s * IFE_NUM_FEATURES + c0) * nb);
       return r;
     };
-    if ((rc = dense_jet_scales(ctx, dI, image_dtype, in.mask, mask_dtype, vol, sigmas, n_sigmas, in.edges, n_edges,
-                               fbytes, [&](int) { return (uint8_t *)ctx->dn_feat.p + off_c; }, box_scale)))
-      return rc;
-    IFE_HIP(ctx, hipMemcpyAsync(counts, ctx->st_out.p, cbytes, hipMemcpyDeviceToHost, ctx->stream));
-    IFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IFE_OK;
+    rc = dense_code_scales(ctx, dI, image_dtype, in.mask, mask_dtype, vol, sigmas, n_sigmas, in.edges, n_edges, fbytes,
+                           [&](int) { return (uint8_t *)ctx->dn_feat.p + off_c; }, box_scale);
+  } else {
+    // at most half of the budget for the features of a group of scales, the box counts get the rest
+    const DenseScalePlan plan = dense_scale_plan(budget / 2, nvox, n_sigmas);
+    const size_t rest = budget > plan.fbytes ? budget - plan.fbytes : 0;
+    auto count_scale = [&](int s, const float *feat, const uint8_t *clamp) {  // into its block of columns
+      return dense_count(ctx, feat, IFE_PLANAR, IFE_NUM_FEATURES, clamp, IFE_U8, g, cen,
+                         in.edges + (size_t)s * IFE_NUM_FEATURES * n_edges, n_edges, (uint32_t *)ctx->st_out.p,
+                         (int64_t)ncol * nb, (int64_t)s * IFE_NUM_FEATURES * nb, rest);
+    };
+    rc = dense_scale_loop(ctx, dI, image_dtype, in.mask, mask_dtype, vol, sigmas, n_sigmas, plan, count_scale);
   }
-  // the budget: at most half for the features of a group of scales, the box counts get the rest
-  size_t budget;
-  if ((rc = dense_budget(ctx, ctx->dn_ws.cap + ctx->dn_feat.cap, &budget))) return rc;
-  const DenseScalePlan plan = dense_scale_plan(budget / 2, nvox, n_sigmas);
-  const size_t rest = budget > plan.fbytes ? budget - plan.fbytes : 0;
-  auto count_scale = [&](int s, const float *feat, const uint8_t *clamp) {  // into its block of columns
-    return dense_count(ctx, feat, IFE_PLANAR, IFE_NUM_FEATURES, clamp, IFE_U8, g, cen,
-                       in.edges + (size_t)s * IFE_NUM_FEATURES * n_edges, n_edges, (uint32_t *)ctx->st_out.p,
-                       (int64_t)ncol * nb, (int64_t)s * IFE_NUM_FEATURES * nb, rest);
-  };
-  if ((rc = dense_scale_loop(ctx, dI, image_dtype, in.mask, mask_dtype, vol, sigmas, n_sigmas, plan, count_scale)))
-    return rc;
+  if (rc) return rc;
   IFE_HIP(ctx, hipMemcpyAsync(counts, ctx->st_out.p, cbytes, hipMemcpyDeviceToHost, ctx->stream));
   IFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return IFE_OK;
@@ -563,7 +549,7 @@ int dense_stream_begin(ife_ctx *ctx, const void *image, int image_dtype, const v
   // (IFE_OPT_DIFFERENTIAL: no feature share -- the labels only, behind the jet workspace, which lies
   // outside the bound as the finite-difference workspace does)
   const bool differential = ctx->differential != 0;
-  if (differential && (rc = jet_reserve(ctx, vol))) return rc;
+  if (differential && (rc = reserve_scales(ctx, vol, true))) return rc;
   size_t budget;
   if ((rc = dense_budget(ctx, ctx->dn_feat.cap, &budget))) return rc;
   const DenseScalePlan plan =
@@ -599,9 +585,9 @@ int dense_stream_begin(ife_ctx *ctx, const void *image, int image_dtype, const v
                       (uint8_t *)ds.codes.p + (size_t)s * IFE_NUM_FEATURES * nvox);
   };
   if (differential)  // the codes straight from the jet into their place
-    rc = dense_jet_scales(ctx, dI, image_dtype, in.mask, mask_dtype, vol, sigmas, n_sigmas, in.edges, n_edges,
-                          plan.fbytes, [&](int s) { return (uint8_t *)ds.codes.p + (size_t)s * IFE_NUM_FEATURES * nvox; },
-                          [](int, const uint8_t *, const uint8_t *) { return (int)IFE_OK; });
+    rc = dense_code_scales(ctx, dI, image_dtype, in.mask, mask_dtype, vol, sigmas, n_sigmas, in.edges, n_edges,
+                           plan.fbytes, [&](int s) { return (uint8_t *)ds.codes.p + (size_t)s * IFE_NUM_FEATURES * nvox; },
+                           [](int, const uint8_t *, const uint8_t *) { return (int)IFE_OK; });
   else
     rc = dense_scale_loop(ctx, dI, image_dtype, in.mask, mask_dtype, vol, sigmas, n_sigmas, plan, code_scale);
   if (rc) return rc;

@@ -1,8 +1,8 @@
 // diff_capi.inc -- the differential normalized convolution complete to second order
 // (include/ife_hip.h: ife_normalized_convolution_jet, ife_differential_features, DESIGN.md
 // section 4 "Differential features"); included at the end of ife_capi.hip (shares its context,
-// staging, line-pass and profiling helpers), in front of stats_capi.inc and dense_capi.inc, whose
-// composite calls come here under IFE_OPT_DIFFERENTIAL.
+// staging, line-pass and profiling helpers), in front of scales_capi.inc, whose scale loop takes the
+// twenty fields of a scale from here and hands them to its sinks.
 //
 // Pass tree.  For f in {cT, c} and every order triple (ox, oy, oz) with ox + oy + oz <= 2 the
 // field F[ox,oy,oz](f) = RG_y^oy(RG_x^ox(RG_z^oz(f))) is built by line passes in ITK's order
@@ -140,19 +140,6 @@ int jet_fields(ife_ctx *ctx, const float *ct, const float *c, const ife_volume_d
   return IFE_OK;
 }
 
-// Vector stores: a misaligned pointer would fault on the device, so it is refused before any work
-// (include/ife_hip.h, IFE_MEM_DEVICE: inputs to their element size, interleaved outputs of eight
-// components to 16 bytes, of ten to 8).
-int jet_check_pointers(ife_ctx *ctx, const void *in0, size_t in0_size, const void *in1, size_t in1_size,
-                       const void *out, int nout, int layout) {
-  if (reinterpret_cast<uintptr_t>(in0) % in0_size || (in1 && reinterpret_cast<uintptr_t>(in1) % in1_size))
-    return fail(ctx, IFE_E_ARG, "input pointers must be aligned to their element size");
-  const uintptr_t need = layout == IFE_PLANAR ? 4 : (nout == 8 ? 16 : 8);
-  if (reinterpret_cast<uintptr_t>(out) % need)
-    return fail(ctx, IFE_E_ARG, "output pointer must be aligned to %d bytes for this layout", (int)need);
-  return IFE_OK;
-}
-
 // What the pointwise kernels need of the volume (pvec is launch_jet's own).
 JetGeom jet_geom(const ife_volume_desc *vol) {
   JetGeom g;
@@ -258,45 +245,6 @@ int jet_sources(ife_ctx *ctx, const TI *img, const TM *msk, int64_t n) {
   return IFE_OK;
 }
 
-// Everything jet_sources and jet_fields allocate for this volume, now: a caller that sizes a budget
-// from the free device memory does so behind it.
-int jet_reserve(ife_ctx *ctx, const ife_volume_desc *vol) {
-  const size_t pitch = ((size_t)(vol->nx * vol->ny * vol->nz) + 3) / 4 * 4;
-  int rc = ensure(ctx, ctx->pre[0], pitch * sizeof(float));
-  if (!rc) rc = ensure(ctx, ctx->pre[1], pitch * sizeof(float));
-  if (!rc) rc = ensure(ctx, ctx->dj_ws, (size_t)JET_SLOTS * pitch * sizeof(float));
-  if (!rc) rc = ensure_ck(ctx, vol, IIR_MAX_JOBS);
-  return rc;
-}
-
-// Every scale of ife_differential_features into dout (device), one after the other; records an
-// event behind each scale into ctx->scale_events when that is set (the scale stream).
-template <typename TI, typename TM>
-int differential_typed(ife_ctx *ctx, const TI *img, const TM *msk, const ife_volume_desc *vol, const float *sigmas,
-                       int n_sigmas, float *dout, int layout) {
-  const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
-  int r = jet_sources(ctx, img, msk, (int64_t)n);
-  for (int s = 0; s < n_sigmas && !r; ++s) {  // one scale after the other over the same workspace
-    JetFields f;
-    r = jet_fields(ctx, (const float *)ctx->pre[0].p, (const float *)ctx->pre[1].p, vol, (double)sigmas[s], &f);
-    if (!r) r = launch_jet<JET_FEATURES8>(ctx, f, msk, dout + (size_t)s * n * IFE_NUM_FEATURES, vol, layout);
-    if (!r && ctx->scale_events) {
-      hipEvent_t e;
-      IFE_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      ctx->scale_events->push_back(e);
-      IFE_HIP(ctx, hipEventRecord(e, ctx->stream));
-    }
-  }
-  return r;
-}
-
-int differential_scales(ife_ctx *ctx, const void *dI, int image_dtype, const void *dM, int mask_dtype,
-                        const ife_volume_desc *vol, const float *sigmas, int n_sigmas, float *dout, int layout) {
-  return with_types(image_dtype, dI, dM != nullptr, mask_dtype, dM, [&](auto img, auto msk) {
-    return differential_typed(ctx, img, msk, vol, sigmas, n_sigmas, dout, layout);
-  });
-}
-
 }  // namespace
 
 extern "C" {
@@ -315,7 +263,8 @@ int ife_normalized_convolution_jet(ife_ctx *ctx, const float *image, const float
   if ((rc = stage_in(ctx, mem, image, n * 4, ctx->st_img, &dI))) return rc;
   if ((rc = stage_in(ctx, mem, certainty, n * 4, ctx->st_aux, &dC))) return rc;
   if ((rc = stage_out_begin(ctx, mem, out10, n * 40, &dO))) return rc;
-  if ((rc = jet_check_pointers(ctx, dI, 4, dC, 4, dO, 10, layout))) return rc;
+  if ((rc = check_in_alignment(ctx, dI, 4, dC, 4))) return rc;
+  if ((rc = check_out_alignment(ctx, dO, 10, layout))) return rc;
   if ((rc = ensure(ctx, ctx->pre[0], (n + 3) / 4 * 4 * sizeof(float)))) return rc;
   float *tc = (float *)ctx->pre[0].p;
   if ((rc = launch_prep<float, float>(ctx, (const float *)dI, (const float *)dC, tc, nullptr, (int64_t)n)))
@@ -324,31 +273,6 @@ int ife_normalized_convolution_jet(ife_ctx *ctx, const float *image, const float
   if ((rc = jet_fields(ctx, tc, (const float *)dC, vol, sigma, &f))) return rc;
   if ((rc = launch_jet<JET_JET10>(ctx, f, (const uint8_t *)nullptr, (float *)dO, vol, layout))) return rc;
   return stage_out_end(ctx, mem, out10, n * 40);
-}
-
-int ife_differential_features(ife_ctx *ctx, const void *image, int image_dtype, const void *mask, int mask_dtype,
-                              const ife_volume_desc *vol, const float *sigmas, int n_sigmas, float *out,
-                              int layout, int mem) {
-  int rc = bind(ctx);
-  if (rc) return rc;
-  if ((rc = emphysema_check(ctx, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, out != nullptr,
-                            layout, mem)))
-    return rc;
-  const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
-  const size_t scale_floats = n * IFE_NUM_FEATURES, out_bytes = scale_floats * 4 * (size_t)n_sigmas;
-  const void *dI, *dM;
-  void *dO;
-  if ((rc = stage_in(ctx, mem, image, n * dtype_size(image_dtype), ctx->st_img, &dI))) return rc;
-  if ((rc = stage_in(ctx, mem, mask, n * (mask ? dtype_size(mask_dtype) : 0), ctx->st_mask, &dM))) return rc;
-  if ((rc = stage_out_begin(ctx, mem, out, out_bytes, &dO))) return rc;
-  if ((rc = jet_check_pointers(ctx, dI, dtype_size(image_dtype), dM, dtype_size(mask_dtype), dO, IFE_NUM_FEATURES,
-                               layout)))
-    return rc;
-  rc = with_types(image_dtype, dI, mask != nullptr, mask_dtype, dM, [&](auto img, auto msk) {
-    return differential_typed(ctx, img, msk, vol, sigmas, n_sigmas, (float *)dO, layout);
-  });
-  if (rc) return rc;
-  return stage_out_end(ctx, mem, out, out_bytes);
 }
 
 }  // extern "C"

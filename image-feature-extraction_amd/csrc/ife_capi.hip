@@ -193,7 +193,6 @@ struct ife_ctx {
   std::vector<hipEvent_t> sc_done;   // one per scale: its feature launch has finished
   hipStream_t sc_copy = nullptr;     // device-to-host copies beside the kernels of later scales
   size_t sc_scale_bytes = 0;
-  std::vector<hipEvent_t> *scale_events = nullptr;  // emphysema_typed records into this when set
   std::vector<ProfRec> prof;
   std::vector<hipEvent_t> ev_pool;
   double acc_ms[KK_COUNT] = {0};
@@ -203,9 +202,6 @@ struct ife_ctx {
 namespace {
 
 void dense_stream_release(ife_ctx *ctx);  // dense_capi.inc
-// diff_capi.inc: every scale of ife_differential_features from device inputs into dout (device)
-int differential_scales(ife_ctx *ctx, const void *dI, int image_dtype, const void *dM, int mask_dtype,
-                        const ife_volume_desc *vol, const float *sigmas, int n_sigmas, float *dout, int layout);
 
 int fail(ife_ctx *ctx, int code, const char *fmt, ...) {
   char buf[512];
@@ -796,9 +792,32 @@ int smooth_group(ife_ctx *ctx, const float *src_num, const float *src_den,
   if (!rc) rc = launch_iir(ctx, v, 1, nj, in, out, sg);
   return rc;
 }
+// Everything smooth_group and the finite-difference scale loop allocate for this volume, now.
+int reserve_smooth(ife_ctx *ctx, const ife_volume_desc *vol) {
+  const size_t nb = (size_t)(vol->nx * vol->ny * vol->nz) * sizeof(float);
+  int rc = ensure_slots(ctx, vol, IFE_MAX_SLOTS);
+  for (int i = 0; i < 2 && !rc; ++i) rc = ensure(ctx, ctx->pre[i], nb);
+  if (!rc) rc = ensure_ck(ctx, vol, 2 * IFE_MAX_SLOTS);
+  return rc;
+}
 // After smooth_group: is slot k's fld[k][0] already the quotient S (denominator folded in)?
 bool slots_hold_quotient(const ife_ctx *ctx, bool has_den) {
   return has_den && ctx->fused_divide && ctx->iir_ckpt == 2;
+}
+
+// Vector loads and stores: a misaligned pointer would fault on the device, so it is refused on the
+// host (include/ife_hip.h, IFE_MEM_DEVICE: inputs to their element size, interleaved outputs of
+// eight components to 16 bytes, of six or ten to 8).  b may be null.
+int check_in_alignment(ife_ctx *ctx, const void *a, size_t a_size, const void *b, size_t b_size) {
+  if (reinterpret_cast<uintptr_t>(a) % a_size || (b && reinterpret_cast<uintptr_t>(b) % b_size))
+    return fail(ctx, IFE_E_ARG, "input pointers must be aligned to their element size");
+  return IFE_OK;
+}
+int check_out_alignment(ife_ctx *ctx, const void *out, int nout, int layout) {
+  const uintptr_t need = layout == IFE_PLANAR ? 4 : (nout == 8 ? 16 : nout % 2 == 0 ? 8 : 4);
+  if (reinterpret_cast<uintptr_t>(out) % need)
+    return fail(ctx, IFE_E_ARG, "output pointer must be aligned to %d bytes for this layout", (int)need);
+  return IFE_OK;
 }
 
 template <int MODE, typename VAL, typename TM>
@@ -828,12 +847,7 @@ int launch_features(ife_ctx *ctx, VAL val, const TM *mask, float *out,
   g.gz = (int)((v->nz + g.zchunk - 1) / g.zchunk);
   const int64_t nblocks = (int64_t)g.gx * g.gy * g.gz;
   if (nblocks > 0x7fffffff) return fail(ctx, IFE_E_SIZE, "volume too large for the feature kernel grid");
-  {  // vector stores: a misaligned pointer would fault on the device, so it is refused here
-    constexpr int nout = FeatNOut<MODE>::value;
-    const uintptr_t need = layout == IFE_PLANAR ? 4 : (nout == 8 ? 16 : nout == 6 ? 8 : 4);
-    if (reinterpret_cast<uintptr_t>(out) % need)
-      return fail(ctx, IFE_E_ARG, "output pointer must be aligned to %d bytes for this layout", (int)need);
-  }
+  if (int rc = check_out_alignment(ctx, out, FeatNOut<MODE>::value, layout)) return rc;
   dim3 grid((unsigned)nblocks, 1, 1);
   ProfScope ps(ctx, KK_FEATURES);
   const bool unit = v->sx == 1.0 && v->sy == 1.0 && v->sz == 1.0;
@@ -981,119 +995,6 @@ int bind(ife_ctx *ctx) {
 
 }  // namespace
 
-// Row f1: instead of a feature volume per scale, the features of the sampled voxels go
-// straight into eight sample columns per scale (stats_capi.inc).
-struct SampleSink {
-  const uint8_t *code;      // per voxel: bit 0 = sample here, bit 1 = label non-zero
-  const uint32_t *seg_base; // exclusive scan of the per-row-segment sample counts
-  float *columns;           // column (scale*8 + k) at columns + (scale*8 + k) * stride
-  int64_t stride, offset;   // elements between columns, samples already in them
-};
-
-template <typename TI, typename TM>
-static int emphysema_typed(ife_ctx *ctx, const TI *img, const TM *msk, const ife_volume_desc *vol,
-                           const float *sigmas, int n_sigmas, float *dout, int layout,
-                           const SampleSink *sink = nullptr) {
-  const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
-  float *tc = (float *)ctx->pre[0].p, *cf = (float *)ctx->pre[1].p;
-  // Cast + Multiply once for all scales (the reference redoes them per scale, a9).
-  // mask == NULL: certainty == 1 everywhere, image*1 is the image and G(1) is exactly
-  // 1.0f at every voxel (DESIGN.md "all-ones certainty"), so the denominator is skipped.
-  // IFE_OPT_Z_SWEEP: no prepass -- the first launch of the Z pass reads image and mask itself,
-  // leaves the same two sources and carries the causal recursions of all scales of a group
-  const bool sweep = ctx->z_sweep && ctx->iir_ckpt == 2;
-  ZSweepSrc zs;
-  zs.img = img; zs.msk = msk;
-  zs.img_dtype = std::is_same<TI, float>::value ? IFE_F32 : IFE_I16;
-  zs.msk_dtype = std::is_same<TM, uint16_t>::value ? IFE_U16 : IFE_U8;
-  zs.tc = tc; zs.cf = cf;
-  zs.nf = msk ? 2 : 1;
-  const float *src_num;
-  if (msk == nullptr && std::is_same<TI, float>::value) {
-    src_num = reinterpret_cast<const float *>(img);
-    zs.write_src = false;  // the backward sweeps read the image
-  } else {
-    if (!sweep) {
-      int rc = launch_prep<TI, TM>(ctx, img, msk, tc, msk ? cf : nullptr, (int64_t)n);
-      if (rc) return rc;
-    }
-    src_num = tc;
-    zs.write_src = true;  // by the first group of scales
-  }
-  for (int s0 = 0; s0 < n_sigmas; s0 += IFE_MAX_SLOTS) {
-    const int ns = std::min(IFE_MAX_SLOTS, n_sigmas - s0);
-    double sg[IFE_MAX_SLOTS];
-    for (int k = 0; k < ns; ++k) sg[k] = (double)sigmas[s0 + k];
-    int rc = smooth_group(ctx, src_num, msk ? cf : nullptr, vol, sg, ns, sweep ? &zs : nullptr);
-    zs.write_src = false;
-    for (int k = 0; k < ns && !rc; ++k) {
-      const bool q = slots_hold_quotient(ctx, msk != nullptr);
-      const ValSmooth vs{(const float *)ctx->fld[k][0].p, msk && !q ? (const float *)ctx->fld[k][2].p : nullptr};
-      if (sink)
-        rc = launch_features<FEAT_SAMPLES8>(ctx, vs, sink->code,
-                                            sink->columns + (size_t)(s0 + k) * IFE_NUM_FEATURES * sink->stride,
-                                            vol, IFE_PLANAR, 0, 0, sink->seg_base, sink->stride, sink->offset);
-      else
-        rc = launch_features<FEAT_FEATURES8>(ctx, vs, msk, dout + (size_t)(s0 + k) * n * IFE_NUM_FEATURES, vol,
-                                             layout);
-      if (!rc && ctx->scale_events) {
-        hipEvent_t e;
-        IFE_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->scale_events->push_back(e);
-        IFE_HIP(ctx, hipEventRecord(e, ctx->stream));
-      }
-    }
-    if (rc) return rc;
-  }
-  return IFE_OK;
-}
-
-// The arguments of ife_emphysema_features and of its streaming form (which has no output yet).
-static int emphysema_check(ife_ctx *ctx, const void *image, int image_dtype, const void *mask, int mask_dtype,
-                           const ife_volume_desc *vol, const float *sigmas, int n_sigmas, bool have_out,
-                           int layout, int mem) {
-  int rc;
-  if ((rc = check_vol(ctx, vol, true))) return rc;
-  if ((rc = check_layout_mem(ctx, layout, mem))) return rc;
-  if (!image || !have_out || !sigmas) return fail(ctx, IFE_E_ARG, "null pointer");
-  if ((rc = check_sigmas(ctx, sigmas, n_sigmas))) return rc;
-  if ((rc = check_image_dtype(ctx, image_dtype))) return rc;
-  return check_mask_dtype(ctx, mask, mask_dtype, true);
-}
-
-// Stage image and mask (HOST mode), then every scale into dout (device), by finite differences or
-// (`differential`) from the jet.  With `uploaded`, an
-// event is recorded behind the uploads and handed to the caller, who waits for it: from
-// page-locked memory the uploads run asynchronously to the host.  *uploaded stays null when this
-// stopped before the scales.
-static int emphysema_staged(ife_ctx *ctx, int mem, const void *image, int image_dtype, const void *mask,
-                            int mask_dtype, const ife_volume_desc *vol, const float *sigmas, int n_sigmas,
-                            float *dout, int layout, hipEvent_t *uploaded = nullptr, bool differential = false) {
-  const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
-  const void *dI, *dM;
-  int rc;
-  if ((rc = stage_in(ctx, mem, image, n * dtype_size(image_dtype), ctx->st_img, &dI))) return rc;
-  if ((rc = stage_in(ctx, mem, mask, n * (mask ? dtype_size(mask_dtype) : 0), ctx->st_mask, &dM))) {
-    if (uploaded) (void)hipStreamSynchronize(ctx->stream);  // the image upload may still read the caller's memory
-    return rc;
-  }
-  if (uploaded) {
-    hipEvent_t e = nullptr;
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess ||
-        hipEventRecord(e, ctx->stream) != hipSuccess) {
-      if (e) (void)hipEventDestroy(e);
-      (void)hipStreamSynchronize(ctx->stream);
-      return fail(ctx, IFE_E_HIP, "upload event: %s", hipGetErrorString(hipGetLastError()));
-    }
-    *uploaded = e;
-  }
-  if (differential)  // IFE_OPT_DIFFERENTIAL in the scale stream: the scales of ife_differential_features
-    return differential_scales(ctx, dI, image_dtype, dM, mask_dtype, vol, sigmas, n_sigmas, dout, layout);
-  return with_types(image_dtype, dI, mask != nullptr, mask_dtype, dM, [&](auto img, auto msk) {
-    return emphysema_typed(ctx, img, msk, vol, sigmas, n_sigmas, dout, layout);
-  });
-}
-
 // =====================================================================================
 extern "C" {
 
@@ -1208,11 +1109,7 @@ int ife_ctx_reserve(ife_ctx *ctx, const ife_volume_desc *vol) {
   if (rc) return rc;
   rc = check_vol(ctx, vol, false);
   if (rc) return rc;
-  const size_t nb = (size_t)(vol->nx * vol->ny * vol->nz) * sizeof(float);
-  rc = ensure_slots(ctx, vol, IFE_MAX_SLOTS);
-  for (int i = 0; i < 2 && !rc; ++i) rc = ensure(ctx, ctx->pre[i], nb);
-  if (!rc) rc = ensure_ck(ctx, vol, 2 * IFE_MAX_SLOTS);
-  return rc;
+  return reserve_smooth(ctx, vol);
 }
 
 int ife_ctx_synchronize(ife_ctx *ctx) {
@@ -1364,81 +1261,6 @@ int ife_differential_normalized_convolution(ife_ctx *ctx, const float *image,
     IFE_HIP(ctx, hipGetLastError());
   }
   return stage_out_end(ctx, mem, out, n * 4);
-}
-
-// ---- a5 + a9 ------------------------------------------------------------------------
-int ife_emphysema_features(ife_ctx *ctx, const void *image, int image_dtype, const void *mask,
-                           int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
-                           int n_sigmas, float *out, int layout, int mem) {
-  int rc = bind(ctx);
-  if (rc) return rc;
-  if ((rc = emphysema_check(ctx, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, out != nullptr,
-                            layout, mem)))
-    return rc;
-  if ((rc = ife_ctx_reserve(ctx, vol))) return rc;
-  const size_t out_bytes = (size_t)(vol->nx * vol->ny * vol->nz) * IFE_NUM_FEATURES * 4 * (size_t)n_sigmas;
-  void *dO;
-  if ((rc = stage_out_begin(ctx, mem, out, out_bytes, &dO))) return rc;
-  rc = emphysema_staged(ctx, mem, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, (float *)dO, layout);
-  if (rc) return rc;
-  return stage_out_end(ctx, mem, out, out_bytes);
-}
-
-// ---- a9, streaming form -------------------------------------------------------------
-int ife_emphysema_features_end(ife_ctx *ctx) {
-  int rc = bind(ctx);
-  if (rc) return rc;
-  IFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->sc_copy) IFE_HIP(ctx, hipStreamSynchronize(ctx->sc_copy));
-  for (auto e : ctx->sc_done) (void)hipEventDestroy(e);
-  ctx->sc_done.clear();
-  IFE_HIP(ctx, ctx->sc_out.reset());
-  ctx->sc_scale_bytes = 0;
-  return IFE_OK;
-}
-
-int ife_emphysema_features_begin(ife_ctx *ctx, const void *image, int image_dtype, const void *mask,
-                                 int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
-                                 int n_sigmas, int layout) {
-  int rc = bind(ctx);
-  if (rc) return rc;
-  if ((rc = emphysema_check(ctx, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, true, layout,
-                            IFE_MEM_HOST)))
-    return rc;
-  if ((rc = ife_emphysema_features_end(ctx))) return rc;  // drop an earlier, unfinished run
-  // the option as it stands now decides for the whole stream: _fetch only copies what is enqueued here
-  const bool differential = ctx->differential != 0;
-  if (!differential && (rc = ife_ctx_reserve(ctx, vol))) return rc;
-  ctx->sc_scale_bytes = (size_t)(vol->nx * vol->ny * vol->nz) * IFE_NUM_FEATURES * sizeof(float);
-  if ((rc = ensure(ctx, ctx->sc_out, ctx->sc_scale_bytes * (size_t)n_sigmas))) return rc;
-  if (!ctx->sc_copy) IFE_HIP(ctx, hipStreamCreateWithFlags(&ctx->sc_copy, hipStreamNonBlocking));
-  // The caller may reuse image and mask once _begin returns, so it waits for the uploads (not for
-  // the scales) before returning.
-  hipEvent_t uploaded = nullptr;
-  ctx->scale_events = &ctx->sc_done;
-  rc = emphysema_staged(ctx, IFE_MEM_HOST, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas,
-                        (float *)ctx->sc_out.p, layout, &uploaded, differential);
-  ctx->scale_events = nullptr;
-  if (!uploaded) return rc;  // stopped before the scales
-  const hipError_t up = hipEventSynchronize(uploaded);
-  (void)hipEventDestroy(uploaded);
-  if (!rc && up != hipSuccess) rc = fail(ctx, IFE_E_HIP, "upload: %s", hipGetErrorString(up));
-  if (rc) (void)ife_emphysema_features_end(ctx);
-  return rc;
-}
-
-int ife_emphysema_features_fetch(ife_ctx *ctx, int scale, float *out) {
-  int rc = bind(ctx);
-  if (rc) return rc;
-  if (!out) return fail(ctx, IFE_E_ARG, "null pointer");
-  if (scale < 0 || scale >= (int)ctx->sc_done.size())
-    return fail(ctx, IFE_E_STATE, "scale %d was not started by ife_emphysema_features_begin (%d scales)",
-                scale, (int)ctx->sc_done.size());
-  IFE_HIP(ctx, hipStreamWaitEvent(ctx->sc_copy, ctx->sc_done[scale], 0));
-  IFE_HIP(ctx, hipMemcpyAsync(out, (const char *)ctx->sc_out.p + (size_t)scale * ctx->sc_scale_bytes,
-                              ctx->sc_scale_bytes, hipMemcpyDeviceToHost, ctx->sc_copy));
-  IFE_HIP(ctx, hipStreamSynchronize(ctx->sc_copy));
-  return IFE_OK;
 }
 
 // ---- a6 -----------------------------------------------------------------------------
@@ -1708,7 +1530,8 @@ int ife_reset_kernel_times(ife_ctx *ctx) {
 
 }  // extern "C"
 
-#include "diff_capi.inc"  // before its users: the sample and dense calls under IFE_OPT_DIFFERENTIAL
+#include "diff_capi.inc"    // the jet of one scale
+#include "scales_capi.inc"  // the scale loop over both paths, before its users: the sample and dense calls
 #include "stats_capi.inc"
 #include "distance_capi.inc"
 #include "dense_capi.inc"

@@ -389,9 +389,9 @@ int ife_bag_image(ife_ctx *ctx, const void *image, int image_dtype, const void *
   uint8_t *clamp = (uint8_t *)(ws + off_m);
   float *feat = (float *)(ws + off_f);
   if ((rc = launch_clamp01(ctx, dM, mask_dtype, clamp, (int64_t)nvox))) return rc;
-  // IFE_OPT_DIFFERENTIAL: the same buffer from the jet (both calls bind and check again)
-  if ((rc = (ctx->differential ? ife_differential_features : ife_emphysema_features)(
-           ctx, dI, image_dtype, clamp, IFE_U8, vol, sigmas, n_sigmas, feat, IFE_PLANAR, IFE_MEM_DEVICE)))
+  // IFE_OPT_DIFFERENTIAL: the same buffer from the jet
+  if ((rc = feature_volumes(ctx, dI, image_dtype, clamp, IFE_U8, vol, sigmas, n_sigmas, feat, IFE_PLANAR,
+                            ctx->differential != 0)))
     return rc;
   // per scale: counts of that scale's 8 histograms for every box, laid out [roi][scale*8+k][bin]
   // through a per-scale scratch [roi][8][bin] and a strided copy back
@@ -519,11 +519,12 @@ int ife_samples_add_image(ife_ctx *ctx, ife_samples *s, const void *image, int i
     return rc;
   if ((rc = ensure(ctx, s->clamp, (size_t)nvox))) return rc;
   if ((rc = launch_clamp01(ctx, dM, mask_dtype, (uint8_t *)s->clamp.p, nvox))) return rc;
+  const bool differential = ctx->differential != 0;
   if (!dIdx) {
     // all-foreground branch, fused: the feature kernel writes the eight features of every
     // sampled voxel straight into the columns (raster order); no feature volume exists
     // (IFE_OPT_DIFFERENTIAL: straight from the jet instead, whose workspace is its own)
-    if (!ctx->differential && (rc = ife_ctx_reserve(ctx, vol))) return rc;
+    if ((rc = reserve_scales(ctx, vol, differential))) return rc;
     for (int c = 1; c < s->ncol; ++c)
       if (s->count[c] != s->count[0]) return fail(ctx, IFE_E_STATE, "columns hold different numbers of samples");
     GatherArgs a;
@@ -557,41 +558,9 @@ int ife_samples_add_image(ife_ctx *ctx, ife_samples *s, const void *image, int i
     if (h == 0) return IFE_OK;
     const int64_t have = s->count[0];
     if ((rc = samples_reserve(s, have + h))) return rc;
-    if (ctx->differential) {
-      // the sources once, then per scale the twenty fields and the sample kernel over them
-      JetSampleSink sk;
-      sk.code = code;
-      sk.seg_base = segs;
-      sk.stride = s->cap;
-      sk.offset = have;
-      sk.nx = (int)vol->nx;
-      sk.gx = gx;
-      sk.nseg = nseg;
-      if (reinterpret_cast<uintptr_t>(dI) % dtype_size(image_dtype))
-        return fail(ctx, IFE_E_ARG, "input pointers must be aligned to their element size");
-      rc = with_types(image_dtype, dI, true, IFE_U8, s->clamp.p, [&](auto img, auto cm) {
-        int r = jet_sources(ctx, img, cm, nvox);
-        for (int i = 0; i < n_sigmas && !r; ++i) {
-          JetFields f;
-          r = jet_fields(ctx, (const float *)ctx->pre[0].p, (const float *)ctx->pre[1].p, vol, (double)sigmas[i], &f);
-          sk.columns = (float *)s->data.p + (size_t)i * IFE_NUM_FEATURES * s->cap;
-          if (!r) r = launch_jet_samples(ctx, f, vol, sk);
-        }
-        return r;
-      });
-      if (rc) return rc;
-      for (int c = 0; c < s->ncol; ++c) s->count[c] = have + h;
-      s->sorted = false;
-      return IFE_OK;
-    }
-    SampleSink sink;
-    sink.code = code;
-    sink.seg_base = segs;
-    sink.columns = (float *)s->data.p;
-    sink.stride = s->cap;
-    sink.offset = have;
+    const ColumnSink sink = {code, segs, (float *)s->data.p, s->cap, have, gx, nseg};
     rc = with_types(image_dtype, dI, true, IFE_U8, s->clamp.p, [&](auto img, auto cm) {
-      return emphysema_typed(ctx, img, cm, vol, sigmas, n_sigmas, nullptr, IFE_PLANAR, &sink);
+      return feature_scales(ctx, img, cm, vol, sigmas, n_sigmas, differential, sink, nullptr);
     });
     if (rc) return rc;
     for (int c = 0; c < s->ncol; ++c) s->count[c] = have + h;
@@ -600,9 +569,8 @@ int ife_samples_add_image(ife_ctx *ctx, ife_samples *s, const void *image, int i
   }
   // sampled branch: the listed voxels are read from a feature volume left in HBM
   if ((rc = ensure(ctx, s->feat, (size_t)nvox * IFE_NUM_FEATURES * n_sigmas * 4))) return rc;
-  if ((rc = (ctx->differential ? ife_differential_features : ife_emphysema_features)(
-           ctx, dI, image_dtype, s->clamp.p, IFE_U8, vol, sigmas, n_sigmas, (float *)s->feat.p, IFE_PLANAR,
-           IFE_MEM_DEVICE)))
+  if ((rc = feature_volumes(ctx, dI, image_dtype, s->clamp.p, IFE_U8, vol, sigmas, n_sigmas, (float *)s->feat.p,
+                            IFE_PLANAR, differential)))
     return rc;
   for (int i = 0; i < n_sigmas && !rc; ++i) {
     const float *f = (const float *)s->feat.p + (size_t)i * nvox * IFE_NUM_FEATURES;

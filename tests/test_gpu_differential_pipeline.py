@@ -372,6 +372,56 @@ def test_option_rules(ctx, ife, synth):
         assert np.array_equal(got[:, 8 * i:8 * i + 8], want)
 
 
+# ---- 9. four scales through every sink, on both paths ----------------------------------------------------------
+FOUR_SIGMAS = [1.0, 1.3, 1.7, 2.2]
+
+
+@pytest.mark.parametrize("option", [0, 1], ids=["finite_differences", "differential"])
+def test_four_scales_through_every_sink(ctx, ife, synth, dense_base, option):
+    """More scales than one group of the finite-difference loop holds (three): the fourth scale comes
+    from a second group, which finds the sources where the first left them and writes behind the
+    columns, volumes and codes of three scales.  Every composite call against the volume call of the
+    same path, which tests/test_gpu_z_sweep.py holds to the oracle at four and five scales; all as
+    uint32 or on integers."""
+    shape, fg = SHAPES[1], (1, 2, 3)
+    img, lab = synth.volume_f32(shape, 630), make_labels(shape)
+    clamped, sel = clamp(lab), np.isin(lab, fg)
+    volume_call = ctx.differential_features if option else ctx.emphysema_features
+    want = volume_call(img, clamped, FOUR_SIGMAS, SPACING)
+    assert len(want) == 4 and int(sel.sum()) > 64
+    c = dense_base
+    dense_clamped = clamp(c["lab"])
+    edges = edges_of(ctx, volume_call(c["img"], dense_clamped, FOUR_SIGMAS), dense_clamped, DENSE_NBINS)
+    assert edges.shape == (32, DENSE_NBINS - 1)
+    dense_args = (c["img"], c["lab"])
+    ctx.set_option(ife.OPT_DIFFERENTIAL, option)
+    try:
+        s = ctx.samples(32)
+        try:
+            s.add_image(img, lab, FOUR_SIGMAS, foreground=fg, spacing=SPACING)
+            assert_columns(s, [want[i][..., k][sel] for i in range(4) for k in range(8)], "four scales")
+        finally:
+            s.close()
+        fetched = list(ctx.emphysema_features_stream(img, clamped, FOUR_SIGMAS, SPACING))
+        single = [ctx.bag_image_dense(*dense_args, [FOUR_SIGMAS[i]], c["size"], edges[8 * i:8 * i + 8], gen_mask=c["gen"])
+                  for i in range(4)]
+        bag = ctx.bag_image_dense(*dense_args, FOUR_SIGMAS, c["size"], edges, gen_mask=c["gen"])
+        blocks = list(ctx.bag_image_dense_stream(*dense_args, FOUR_SIGMAS, c["size"], edges, gen_mask=c["gen"],
+                                                 values="counts"))
+    finally:
+        ctx.set_option(ife.OPT_DIFFERENTIAL, 0)
+    assert len(fetched) == 4
+    for i in range(4):
+        assert np.array_equal(bits(fetched[i]), bits(want[i])), "scale stream, scale %d" % i
+    assert bag.dtype == np.uint32 and bag.shape == (len(c["want"]), 32, DENSE_NBINS)
+    streamed = dense_stream.joined(blocks, len(bag))
+    assert streamed.dtype == np.uint32
+    for i in range(4):
+        assert single[i].shape == (len(bag), 8, DENSE_NBINS) and (single[i].sum(-1) > 0).any()
+        assert np.array_equal(bag[:, 8 * i:8 * i + 8], single[i]), "dense bag, scale %d" % i
+        assert np.array_equal(streamed[:, 8 * i:8 * i + 8], single[i]), "dense stream, scale %d" % i
+
+
 # ---- 10. the tools under IFE_DIFFERENTIAL ---------------------------------------------------------------------
 TOOL_SHAPE, TOOL_SCALES, TOOL_NBINS = (12, 20, 24), [1.0, 2.5], 5
 
