@@ -64,6 +64,7 @@ EXPORTS = (
     "ife_samples_equalized_edges", "ife_samples_read_column",
     "ife_signed_distance_map", "ife_expected_distance",
     "ife_stage_recursive_gaussian_order", "ife_normalized_convolution_jet", "ife_differential_features",
+    "ife_deflate_bound", "ife_deflate", "ife_emphysema_features_fetch_deflated",
 )
 
 
@@ -193,6 +194,12 @@ def load_library():
     lib.ife_normalized_convolution_jet.argtypes = [vp, f32p, f32p, vd, C.c_double, f32p, i32, i32]
     lib.ife_differential_features.argtypes = [vp, vp, i32, vp, i32, vd, C.POINTER(C.c_float), i32,
                                               f32p, i32, i32]
+    lib.ife_deflate_bound.argtypes = [C.c_size_t]
+    lib.ife_deflate_bound.restype = C.c_size_t
+    lib.ife_deflate.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t),
+                                C.POINTER(C.c_uint32), i32]
+    lib.ife_emphysema_features_fetch_deflated.argtypes = [vp, i32, i32, vp, C.c_size_t,
+                                                          C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]
     _lib = lib
     return lib
 
@@ -242,6 +249,49 @@ def _ptr_array(ptrs):
 
 def _double_array(values):
     return (C.c_double * len(values))(*[float(v) for v in values])
+
+
+class ScaleStream:
+    """The scale stream of a context (ife_emphysema_features_begin / _fetch / _fetch_deflated /
+    _end) as a context manager: every scale is enqueued on entry and stays on the device until
+    exit; fetch and fetch_deflated wait for their scale only."""
+
+    def __init__(self, ctx, image, mask, sigmas, spacing, layout):
+        self._ctx, self._layout = ctx, layout
+        self._image, self._idt = _image_arg(image)
+        self._mask, self._mdt, self._mptr = _mask_arg(mask)
+        self._desc = _desc(self._image.shape, spacing)
+        self._sig, self.n_scales = _sigma_arg(sigmas), len(sigmas)
+        self._open = False
+
+    def __enter__(self):
+        c = self._ctx
+        c._chk(c._lib.ife_emphysema_features_begin(
+            c._h, self._image.ctypes.data, self._idt, self._mptr, self._mdt, C.byref(self._desc),
+            self._sig, self.n_scales, self._layout))
+        self._open = True
+        return self
+
+    def __exit__(self, *a):
+        if self._open:
+            self._open = False
+            self._ctx._chk(self._ctx._lib.ife_emphysema_features_end(self._ctx._h))
+
+    def fetch(self, scale):
+        shp = self._image.shape
+        out = np.empty(shp + (8,) if self._layout == INTERLEAVED else (8,) + shp, np.float32)
+        self._ctx._chk(self._ctx._lib.ife_emphysema_features_fetch(self._ctx._h, int(scale), out.ctypes.data))
+        return out
+
+    def fetch_deflated(self, scale, component):
+        """(DEFLATE blocks, CRC-32) of one component plane of a planar stream."""
+        c = self._ctx
+        cap = c.deflate_bound(self._image.size * 4)
+        out = np.empty(cap, np.uint8)
+        n, crc = C.c_size_t(), C.c_uint32()
+        c._chk(c._lib.ife_emphysema_features_fetch_deflated(
+            c._h, int(scale), int(component), out.ctypes.data, cap, C.byref(n), C.byref(crc)))
+        return out[:n.value].tobytes(), int(crc.value)
 
 
 class Context:
@@ -424,6 +474,42 @@ class Context:
                 yield out
         finally:
             self._chk(self._lib.ife_emphysema_features_end(self._h))
+
+    def scale_stream(self, image, mask, sigmas, spacing=(1.0, 1.0, 1.0), layout=PLANAR):
+        """The scale stream as an object: ``with ctx.scale_stream(...) as st``, then
+        st.fetch(scale) -> (8, nz, ny, nx) and, on a planar stream, st.fetch_deflated(scale,
+        component) -> (DEFLATE blocks, CRC-32 of the plane), in any order, until the block is
+        left."""
+        return ScaleStream(self, image, mask, sigmas, spacing, layout)
+
+    # ---- DEFLATE blocks formed on the device --------------------------------
+    def deflate_bound(self, nbytes):
+        return int(self._lib.ife_deflate_bound(int(nbytes)))
+
+    def deflate(self, array):
+        """(blocks, crc) of the bytes of `array`: complete non-final DEFLATE blocks (a raw stream
+        with 03 00 appended) and the CRC-32 of the input (ife_deflate)."""
+        a = np.ascontiguousarray(array)
+        cap = self.deflate_bound(a.nbytes)
+        out = np.empty(max(cap, 1), np.uint8)
+        src = a if a.nbytes else np.zeros(1, np.uint8)
+        n, crc = C.c_size_t(), C.c_uint32()
+        self._chk(self._lib.ife_deflate(self._h, src.ctypes.data, a.nbytes, out.ctypes.data, cap,
+                                        C.byref(n), C.byref(crc), MEM_HOST))
+        return out[:n.value].tobytes(), int(crc.value)
+
+    def deflate_device(self, ptr, nbytes, out_ptr, capacity):
+        """ife_deflate over device pointers of any byte alignment: (bytes written, crc).  IfeError
+        E_SIZE when `capacity` is too small; nothing is written then."""
+        n, crc = C.c_size_t(), C.c_uint32()
+        rc = self._lib.ife_deflate(self._h, C.c_void_p(ptr), int(nbytes), C.c_void_p(out_ptr),
+                                   int(capacity), C.byref(n), C.byref(crc), MEM_DEVICE)
+        if rc == E_SIZE:
+            err = IfeError(rc, self._lib.ife_last_error(self._h).decode())
+            err.needed = int(n.value)  # the size the blocks take
+            raise err
+        self._chk(rc)
+        return int(n.value), int(crc.value)
 
     def fd_hessian_features(self, image, mask=None, spacing=(1.0, 1.0, 1.0), layout=INTERLEAVED):
         image, idt = _image_arg(image)

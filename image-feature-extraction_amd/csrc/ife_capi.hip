@@ -25,6 +25,7 @@
 #include "distance_kernels.hpp"
 #include "dense_kernels.hpp"
 #include "dense_plan.hpp"
+#include "deflate_kernels.hpp"
 #define IFE_IIR_NS iir_exact
 #define IFE_IIR_FMA 0
 #include "iir_kernels.inc"
@@ -193,6 +194,10 @@ struct ife_ctx {
   std::vector<hipEvent_t> sc_done;   // one per scale: its feature launch has finished
   hipStream_t sc_copy = nullptr;     // device-to-host copies beside the kernels of later scales
   size_t sc_scale_bytes = 0;
+  int sc_layout = IFE_INTERLEAVED;   // of the stream's _begin: the deflated fetch needs whole planes
+  // DEFLATE on the device (deflate_capi.inc): offsets, counts and CRC pieces of the chunks, and the
+  // blocks of a plane of the stream on their way to the host
+  DevBuf df_ws, df_out;
   std::vector<ProfRec> prof;
   std::vector<hipEvent_t> ev_pool;
   double acc_ms[KK_COUNT] = {0};
@@ -1532,6 +1537,7 @@ int ife_reset_kernel_times(ife_ctx *ctx) {
 
 #include "diff_capi.inc"    // the jet of one scale
 #include "scales_capi.inc"  // the scale loop over both paths, before its users: the sample and dense calls
+#include "deflate_capi.inc"  // reads the scale stream
 #include "stats_capi.inc"
 #include "distance_capi.inc"
 #include "dense_capi.inc"

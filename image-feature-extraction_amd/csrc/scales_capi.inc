@@ -230,6 +230,7 @@ int ife_emphysema_features_end(ife_ctx *ctx) {
   for (auto e : ctx->sc_done) (void)hipEventDestroy(e);
   ctx->sc_done.clear();
   IFE_HIP(ctx, ctx->sc_out.reset());
+  IFE_HIP(ctx, ctx->df_out.reset());  // the blocks of the deflated fetch (deflate_capi.inc)
   ctx->sc_scale_bytes = 0;
   return IFE_OK;
 }
@@ -247,6 +248,7 @@ int ife_emphysema_features_begin(ife_ctx *ctx, const void *image, int image_dtyp
   const bool differential = ctx->differential != 0;
   const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
   ctx->sc_scale_bytes = n * IFE_NUM_FEATURES * sizeof(float);
+  ctx->sc_layout = layout;
   if ((rc = ensure(ctx, ctx->sc_out, ctx->sc_scale_bytes * (size_t)n_sigmas))) return rc;
   if (!ctx->sc_copy) IFE_HIP(ctx, hipStreamCreateWithFlags(&ctx->sc_copy, hipStreamNonBlocking));
   // The caller may reuse image and mask once _begin returns, so it waits for the uploads (not for

@@ -29,6 +29,12 @@
 // that one for every tool), so announced scales stream through begin/fetch on this path as on the
 // default one; without them every Update() is one self-contained call.  With several devices
 // (IFE_DEVICES) it throws.
+//
+// A third addition: FetchDeflated(component, blocks, crc) hands out one component plane of the
+// current sigma (one of the announced scales) as DEFLATE blocks formed on the device
+// (ife_emphysema_features_fetch_deflated), for a writer that only has to put a gzip header and
+// trailer around them (io_detail::write_nifti_gz_blocks).  The stream is begun planar for that,
+// so Update() and FetchDeflated() of one filter restart it when they alternate.  One device only.
 #ifndef __ImageToEmphysemaFeaturesFilter_h
 #define __ImageToEmphysemaFeaturesFilter_h
 
@@ -108,15 +114,9 @@ class ImageToEmphysemaFeaturesFilter {
       dirty_ = false;
       return;
     }
-    // the filter's switch is the context's option while its own calls run (_begin reads it)
-    struct OptionScope {
-      ife_ctx *c;
-      OptionScope(ife_ctx *ctx, bool on) : c(ctx) { (void)ife_ctx_set_option(c, IFE_OPT_DIFFERENTIAL, on ? 1 : 0); }
-      ~OptionScope() {
-        (void)ife_ctx_set_option(c, IFE_OPT_DIFFERENTIAL, ife::host::Engine::DifferentialFromEnvironment() ? 1 : 0);
-      }
-    } scope(e.ctx(), differential_);
+    OptionScope scope(e.ctx(), differential_);
     if (which >= 0) {  // the announced schedule: everything is started once, fetched per scale
+      if (streaming_ && planar_) EndStream();
       if (!streaming_) {
         e.check(ife_emphysema_features_begin(
                     e.ctx(), image_->GetBufferPointer(), ife::host::ImageDType<PixelType>::value,
@@ -141,6 +141,31 @@ class ImageToEmphysemaFeaturesFilter {
     dirty_ = false;
   }
   void UpdateLargestPossibleRegion() { Update(); }
+  // Component `component` of the scale GetSigma() as DEFLATE blocks and the CRC-32 of its bytes.
+  void FetchDeflated(unsigned int component, std::vector<unsigned char> &blocks, uint32_t &crc) {
+    const char *where = "ImageToEmphysemaFeaturesFilter";
+    if (!image_ || !mask_) throw ExceptionObject("Input image and mask are required", where);
+    ife::host::same_size(*image_, *mask_, where);
+    if (ife::host::Engine::devices().size() > 1)
+      throw ExceptionObject("DEFLATE on the device runs on one device; unset IFE_DEVICES", where);
+    int which = -1;
+    for (size_t k = 0; k < scales_.size(); ++k)
+      if (scales_[k] == (float)sigma_) { which = (int)k; break; }
+    if (which < 0) throw ExceptionObject("FetchDeflated needs the scales announced with SetScales", where);
+    ife::host::Engine &e = ife::host::Engine::Instance();
+    const ife_volume_desc d = ife::host::describe(*image_);
+    OptionScope scope(e.ctx(), differential_);
+    if (streaming_ && !planar_) EndStream();
+    if (!streaming_) {
+      e.check(ife_emphysema_features_begin(
+                  e.ctx(), image_->GetBufferPointer(), ife::host::ImageDType<PixelType>::value,
+                  mask_->GetBufferPointer(), ife::host::MaskDType<typename InputMaskType::PixelType>::value, &d,
+                  scales_.data(), (int)scales_.size(), IFE_PLANAR),
+              where);
+      streaming_ = planar_ = true;
+    }
+    e.fetch_deflated(which, (int)component, (size_t)(d.nx * d.ny * d.nz) * sizeof(float), blocks, crc, where);
+  }
   OutputImageType *GetOutput() {
     if (out_.IsNull()) out_ = OutputImageType::New();
     return out_.GetPointer();
@@ -152,11 +177,20 @@ class ImageToEmphysemaFeaturesFilter {
       ife::host::Engine &e = ife::host::Engine::Instance();
       if (ife_multi *multi = e.multi()) (void)ife_multi_emphysema_features_end(multi);
       else (void)ife_emphysema_features_end(e.ctx());
-      streaming_ = false;
+      streaming_ = planar_ = false;
     }
   }
+  // the filter's switch is the context's option while its own calls run (_begin reads it)
+  struct OptionScope {
+    ife_ctx *c;
+    OptionScope(ife_ctx *ctx, bool on) : c(ctx) { (void)ife_ctx_set_option(c, IFE_OPT_DIFFERENTIAL, on ? 1 : 0); }
+    ~OptionScope() {
+      (void)ife_ctx_set_option(c, IFE_OPT_DIFFERENTIAL, ife::host::Engine::DifferentialFromEnvironment() ? 1 : 0);
+    }
+  };
   std::vector<float> scales_;
   bool streaming_ = false;
+  bool planar_ = false;  // the stream was begun for FetchDeflated
   const InputImageType *image_ = nullptr;
   const InputMaskType *mask_ = nullptr;
   ScalarRealType sigma_ = 1.0;  // .hxx:18

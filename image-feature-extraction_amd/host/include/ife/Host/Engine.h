@@ -60,6 +60,25 @@ class Engine {
   void check(int rc, const char *where) {
     if (rc != IFE_OK) throw itk::ExceptionObject(ife_last_error(ctx_), where);
   }
+  // One component plane (plane_bytes bytes) of a scale of the context's planar scale stream as
+  // DEFLATE blocks formed on the device, and the CRC-32 of the plane.  The blocks arrive in a
+  // buffer of the largest size they can take, kept for the next call, and leave in `blocks` at
+  // their own size.
+  void fetch_deflated(int scale, int component, size_t plane_bytes, std::vector<unsigned char> &blocks,
+                      uint32_t &crc, const char *where) {
+    deflate_buf_.resize(ife_deflate_bound(plane_bytes));
+    size_t n = 0;
+    check(ife_emphysema_features_fetch_deflated(ctx(), scale, component, deflate_buf_.data(), deflate_buf_.size(),
+                                                &n, &crc),
+          where);
+    blocks.assign(deflate_buf_.begin(), deflate_buf_.begin() + (std::ptrdiff_t)n);
+  }
+  // IFE_DEVICE_GZIP (unset, empty or "0": off): ExtractFeatures takes its .nii.gz payloads as
+  // DEFLATE blocks from the device.  One device only.
+  static bool DeviceGzipFromEnvironment() {
+    const char *v = std::getenv("IFE_DEVICE_GZIP");
+    return v && v[0] && std::strcmp(v, "0") != 0;
+  }
   // IFE_DEVICES=0,1,2,3: the feature filter cuts the volume into Z-slabs over these devices
   // (ife_multi_*, one host thread, peer copies).  Unset or one entry: nullptr.
   ife_multi *multi() {
@@ -88,6 +107,7 @@ class Engine {
   ife_ctx *ctx_ = nullptr;
   ife_multi *multi_ = nullptr;
   bool multi_tried_ = false;
+  std::vector<unsigned char> deflate_buf_;
 };
 
 inline ife_volume_desc describe(const itk::ImageBase3 &img) {

@@ -231,8 +231,8 @@ inline void convert_any(const RawVolume &v, TOut *dst) {
   }
 }
 
-template <typename T>
-inline void write_nifti(const std::string &path, const ImageBase3 &info, const T *data) {
+// The header of a volume of NIfTI datatype `datatype` (bytes_per_voxel each) with info's geometry.
+inline Nifti1Header nifti_header(const std::string &path, const ImageBase3 &info, int datatype, size_t bytes_per_voxel) {
   Nifti1Header h;
   std::memset(&h, 0, sizeof h);
   h.sizeof_hdr = 348;
@@ -247,8 +247,8 @@ inline void write_nifti(const std::string &path, const ImageBase3 &info, const T
   }
   for (int a = 4; a < 8; ++a) h.dim[a] = 1;
   h.pixdim[0] = 1.0f;
-  h.datatype = (int16_t)NiftiCode<T>::value;
-  h.bitpix = (int16_t)(8 * sizeof(T));
+  h.datatype = (int16_t)datatype;
+  h.bitpix = (int16_t)(8 * bytes_per_voxel);
   h.vox_offset = 352.0f;
   h.scl_slope = 1.0f;
   h.xyzt_units = 2;  // mm
@@ -273,6 +273,58 @@ inline void write_nifti(const std::string &path, const ImageBase3 &info, const T
     h.xyzt_units = fg.xyzt_units;
   }
   std::memcpy(h.magic, "n+1", 4);
+  return h;
+}
+
+// One gzip member around DEFLATE blocks that were formed elsewhere (ife_deflate: complete,
+// non-final blocks that end on a byte boundary): the ten header bytes, `head` (what precedes the
+// payload in the file, at most 65535 bytes) as one stored block, the payload's blocks, an empty
+// final block (03 00), then the CRC-32 and the length modulo 2^32 of head + payload.  payload_crc
+// is the CRC-32 of the payload_bytes bytes the blocks inflate to.
+inline void append_gzip_member(std::vector<unsigned char> &out, const unsigned char *head, size_t head_bytes,
+                               const unsigned char *blocks, size_t block_bytes, uint32_t payload_crc,
+                               uint64_t payload_bytes) {
+  if (head_bytes > 65535) throw ExceptionObject("a stored block holds at most 65535 bytes", "append_gzip_member");
+  const unsigned char magic[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};
+  out.reserve(out.size() + 10 + 5 + head_bytes + block_bytes + 2 + 8);
+  out.insert(out.end(), magic, magic + 10);
+  auto le = [&out](uint32_t v, int bytes) {
+    for (int i = 0; i < bytes; ++i) out.push_back((unsigned char)(v >> (8 * i)));
+  };
+  out.push_back(0);  // BFINAL 0, BTYPE 00
+  le((uint32_t)head_bytes, 2);
+  le(~(uint32_t)head_bytes & 0xffffu, 2);
+  if (head_bytes) out.insert(out.end(), head, head + head_bytes);
+  if (block_bytes) out.insert(out.end(), blocks, blocks + block_bytes);
+  out.push_back(3);  // BFINAL 1, BTYPE 01, end of block
+  out.push_back(0);
+  const uLong head_crc = crc32(crc32(0L, Z_NULL, 0), head_bytes ? head : Z_NULL, (uInt)head_bytes);
+  le((uint32_t)crc32_combine(head_crc, (uLong)payload_crc, (z_off_t)payload_bytes), 4);
+  le((uint32_t)((head_bytes + payload_bytes) & 0xffffffffu), 4);
+}
+
+// A .nii.gz of float voxels whose payload arrives as DEFLATE blocks (same decoded contents as
+// write_nifti of the same volume).
+inline void write_nifti_gz_blocks(const std::string &path, const ImageBase3 &info, const unsigned char *blocks,
+                                  size_t block_bytes, uint32_t payload_crc) {
+  const Nifti1Header h = nifti_header(path, info, NiftiCode<float>::value, sizeof(float));
+  unsigned char head[352] = {0};  // the header and the four bytes of the empty extension
+  std::memcpy(head, &h, sizeof h);
+  const Size3 &sz = info.GetLargestPossibleRegion().GetSize();
+  std::vector<unsigned char> member;
+  append_gzip_member(member, head, sizeof head, blocks, block_bytes, payload_crc,
+                     (uint64_t)(sz[0] * sz[1] * sz[2]) * sizeof(float));
+  std::ofstream f(path, std::ios::binary);
+  if (!f) throw ExceptionObject("cannot create " + path, "ImageFileWriter");
+  f.write(reinterpret_cast<const char *>(member.data()), (std::streamsize)member.size());
+  f.close();
+  if (!f) throw ExceptionObject("write failed: " + path, "ImageFileWriter");
+}
+
+template <typename T>
+inline void write_nifti(const std::string &path, const ImageBase3 &info, const T *data) {
+  const Nifti1Header h = nifti_header(path, info, NiftiCode<T>::value, sizeof(T));
+  const Size3 &sz = info.GetLargestPossibleRegion().GetSize();
   const unsigned char ext[4] = {0, 0, 0, 0};
   const size_t nb = (size_t)(sz[0] * sz[1] * sz[2]) * sizeof(T);
   if (ends_with(path, ".gz")) {

@@ -3,6 +3,8 @@
 // <out>_scale_<std::to_string(scale)><FeatureName>.nii.gz).  The arithmetic runs on the
 // MI355X through libife_hip.so; the eight files of a scale are compressed and written on
 // worker threads while the device computes the next scale (ife/Host/AsyncWriter.h).
+// With IFE_DEVICE_GZIP=1 (and .nii.gz output) the planes are compressed on the device instead
+// (ife_emphysema_features_fetch_deflated) and the host only frames and writes them.
 #include <iostream>
 
 #include "tclap/CmdLine.h"
@@ -73,11 +75,21 @@ int main(int argc, char *argv[]) {
     featureFilter->SetInputMask(clampFilter->GetOutput());
     indexSelectionFilter->SetInput(featureFilter->GetOutput());
     featureFilter->SetScales(scales);  // all scales start on the device at the first Update()
+    // IFE_DEVICE_GZIP=1: the device forms the DEFLATE blocks of every component plane and only
+    // they cross to the host, which puts the gzip header and trailer around them
+    const bool deviceGzip = ife::host::Engine::DeviceGzipFromEnvironment() && outFileType() == ".nii.gz";
+    std::vector<unsigned char> blocks;
     for (auto scale : scales) {
       featureFilter->SetSigma(scale);
       for (unsigned int i = 0; i < featureNames.size(); ++i) {
         indexSelectionFilter->SetIndex(i);
         outPath = outBasePath + "_scale_" + std::to_string(scale) + featureNames[i] + outFileType();
+        if (deviceGzip) {
+          uint32_t crc = 0;
+          featureFilter->FetchDeflated(i, blocks, crc);
+          itk::io_detail::write_nifti_gz_blocks(outPath, *reader->GetOutput(), blocks.data(), blocks.size(), crc);
+          continue;
+        }
         featureFilter->UpdateLargestPossibleRegion();
         indexSelectionFilter->Update();
         // hand the selected component to the writers; the filter makes a new image next time

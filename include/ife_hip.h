@@ -289,6 +289,41 @@ int ife_emphysema_features_begin(ife_ctx *ctx, const void *image, int image_dtyp
 int ife_emphysema_features_fetch(ife_ctx *ctx, int scale, float *out);
 int ife_emphysema_features_end(ife_ctx *ctx);
 
+/* ---- DEFLATE blocks formed on the device (row f3: the volume writer's compression) ----
+ *
+ * ife_deflate turns `bytes` bytes into complete, non-final DEFLATE blocks (RFC 1951) that start
+ * and end on a byte boundary: with 03 00 appended they are a raw DEFLATE stream that any inflater
+ * accepts, and a gzip member once a header in front and CRC-32 and length behind are added.  The
+ * output depends on the input bytes alone.
+ *
+ * The format.  The input is cut into chunks of 32768 bytes (the last may be shorter); the blocks
+ * of the chunks are concatenated in order.  Tokens of a chunk [lo, hi): eq[i] holds when i >= 4
+ * and b[i] == b[i-4] (i counts from the start of the input, so a match may reach back over the
+ * chunk start).  Where eq is false the byte is a literal.  A maximal run [i, j) of true eq with
+ * j <= hi (a run running at lo starts at lo) of length L >= 3 becomes matches of distance 4 and
+ * length min(258, rest) while rest >= 3, and the 0, 1 or 2 bytes left over are literals; a run
+ * shorter than 3 is literals.  Form F: one block with the fixed Huffman codes (BFINAL 0, BTYPE
+ * 01), the tokens, end of block, then an empty stored block to realign (three zero bits, zero
+ * padding to the byte boundary, 00 00 FF FF).  Form S: one stored block, 00, LEN, NLEN, the
+ * chunk's bytes: 5 + len bytes.  A chunk takes S when S is not longer than F, so the output is at
+ * most ife_deflate_bound(bytes) = bytes + 5 * ceil(bytes / 32768) bytes; no input gives no output.
+ *
+ * `data` and `out` follow `mem` and may have any byte alignment, on the device too; `out_bytes`
+ * and `crc32` are host scalars, *crc32 the CRC-32 (IEEE, as zlib's crc32) of the input.  The call
+ * blocks.  A `capacity` below the size of the blocks returns IFE_E_SIZE with the needed size in
+ * *out_bytes and nothing written to `out`. */
+size_t ife_deflate_bound(size_t bytes);
+int ife_deflate(ife_ctx *ctx, const void *data, size_t bytes, void *out, size_t capacity,
+                size_t *out_bytes, uint32_t *crc32, int mem);
+
+/* One component plane (0 .. 7) of a scale of the stream as the blocks of ife_deflate, to host
+ * memory: between ife_emphysema_features_begin with IFE_PLANAR (IFE_E_STATE for an interleaved
+ * stream, whose components are not contiguous) and _end.  It waits for that scale on the stream's
+ * copy stream, forms the blocks there and copies only them, so later scales keep computing.
+ * `capacity`, `out_bytes` and `crc32` as in ife_deflate. */
+int ife_emphysema_features_fetch_deflated(ife_ctx *ctx, int scale, int component, void *out,
+                                          size_t capacity, size_t *out_bytes, uint32_t *crc32);
+
 /* ---- a6 / a7 / a8: tool bodies ---------------------------------------------------- */
 
 /* Body of tools/FiniteDifference_HessianFeatures.cxx:126-229 (un-smoothed Hessian,
