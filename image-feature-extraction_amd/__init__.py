@@ -65,6 +65,8 @@ EXPORTS = (
     "ife_signed_distance_map", "ife_expected_distance",
     "ife_stage_recursive_gaussian_order", "ife_normalized_convolution_jet", "ife_differential_features",
     "ife_deflate_bound", "ife_deflate", "ife_emphysema_features_fetch_deflated",
+    "ife_stage_z_sweep_order", "ife_stage_z_combine_order", "ife_stage_z_fused_order",
+    "ife_stage_jet_features", "ife_multi_differential_features", "ife_multi_differential_features_begin",
 )
 
 
@@ -143,6 +145,13 @@ def load_library():
                                         C.POINTER(C.c_double), i32, i32, C.POINTER(vp)]
     lib.ife_stage_z_fused.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(vp), vd, i64, i64,
                                       C.POINTER(C.c_double), i32, i32, vp, vp, C.POINTER(vp)]
+    lib.ife_stage_z_sweep_order.argtypes = [vp, i32, i32, C.POINTER(vp), vd, i64, i64,
+                                            C.POINTER(C.c_double), C.POINTER(i32), i32, vp, vp, C.POINTER(vp)]
+    lib.ife_stage_z_combine_order.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), vd, i64, i64,
+                                              C.POINTER(C.c_double), C.POINTER(i32), i32, i32, C.POINTER(vp)]
+    lib.ife_stage_z_fused_order.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(vp), vd, i64, i64,
+                                            C.POINTER(C.c_double), C.POINTER(i32), i32, i32, vp, vp, C.POINTER(vp)]
+    lib.ife_stage_jet_features.argtypes = [vp, C.POINTER(vp), vp, i32, vd, C.c_double, vp, i32]
     lib.ife_stage_recursive_gaussian_quotient.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                                           vd, i32, C.POINTER(C.c_double)]
     lib.ife_multi_create.argtypes = [C.POINTER(i32), i32, C.POINTER(vp)]
@@ -155,6 +164,8 @@ def load_library():
     lib.ife_multi_emphysema_features_begin.argtypes = [vp, vp, i32, vp, i32, vd, C.POINTER(C.c_float), i32, i32]
     lib.ife_multi_emphysema_features_fetch.argtypes = [vp, i32, f32p]
     lib.ife_multi_emphysema_features_end.argtypes = [vp]
+    lib.ife_multi_differential_features.argtypes = lib.ife_multi_emphysema_features.argtypes
+    lib.ife_multi_differential_features_begin.argtypes = lib.ife_multi_emphysema_features_begin.argtypes
     lib.ife_get_kernel_times.argtypes = [vp, C.POINTER(KernelTime), i32]
     lib.ife_reset_kernel_times.argtypes = [vp]
     lib.ife_measure_stream.argtypes = [vp, i32, vp, vp, C.c_size_t, i32, C.POINTER(C.c_double)]
@@ -245,6 +256,13 @@ def _size_arg(size_xyz):
 
 def _ptr_array(ptrs):
     return (C.c_void_p * len(ptrs))(*ptrs)
+
+
+def _order_array(orders):
+    """Per-job orders of the recursive Gaussian; None is the C NULL (all zero)."""
+    if orders is None:
+        return None
+    return (C.c_int * len(orders))(*[int(o) for o in orders])
 
 
 def _double_array(values):
@@ -678,6 +696,44 @@ class Context:
             int(line0), int(nlines), _double_array(sigmas), int(bool(has_lo)), int(bool(has_hi)),
             C.c_void_p(state_in_ptr or 0), C.c_void_p(state_out_ptr), _ptr_array(ck_ptrs)))
 
+    def stage_z_sweep_order(self, direction, in_ptrs, slab_shape_zyx, spacing, line0, nlines, sigmas,
+                            orders, has_neighbour, state_in_ptr, state_out_ptr, ck_ptrs):
+        """stage_z_sweep with an order (0, 1, 2) per job; orders None = all zero.  Three
+        consecutive jobs with the same input, the same sigma and the orders 0, 1, 2 read every
+        plane once."""
+        d = _desc(slab_shape_zyx, spacing)
+        self._chk(self._lib.ife_stage_z_sweep_order(
+            self._h, int(direction), len(in_ptrs), _ptr_array(in_ptrs), C.byref(d), int(line0), int(nlines),
+            _double_array(sigmas), _order_array(orders), int(bool(has_neighbour)),
+            C.c_void_p(state_in_ptr or 0), C.c_void_p(state_out_ptr), _ptr_array(ck_ptrs)))
+
+    def stage_z_combine_order(self, in_ptrs, out_ptrs, slab_shape_zyx, spacing, line0, nlines, sigmas,
+                              orders, has_lo, has_hi, ck_ptrs):
+        d = _desc(slab_shape_zyx, spacing)
+        self._chk(self._lib.ife_stage_z_combine_order(
+            self._h, len(in_ptrs), _ptr_array(in_ptrs), _ptr_array(out_ptrs), C.byref(d), int(line0),
+            int(nlines), _double_array(sigmas), _order_array(orders), int(bool(has_lo)), int(bool(has_hi)),
+            _ptr_array(ck_ptrs)))
+
+    def stage_z_fused_order(self, direction, in_ptrs, out_ptrs, slab_shape_zyx, spacing, line0, nlines,
+                            sigmas, orders, has_lo, has_hi, state_in_ptr, state_out_ptr, ck_ptrs):
+        d = _desc(slab_shape_zyx, spacing)
+        self._chk(self._lib.ife_stage_z_fused_order(
+            self._h, int(direction), len(in_ptrs), _ptr_array(in_ptrs), _ptr_array(out_ptrs), C.byref(d),
+            int(line0), int(nlines), _double_array(sigmas), _order_array(orders), int(bool(has_lo)),
+            int(bool(has_hi)), C.c_void_p(state_in_ptr or 0), C.c_void_p(state_out_ptr), _ptr_array(ck_ptrs)))
+
+    def stage_jet_features(self, zf_ptrs, mask_ptr, mask_dtype, slab_shape_zyx, spacing, sigma, out_ptr,
+                           layout=INTERLEAVED):
+        """X level, Y level and pointwise pass of differential_features on a slab, from its six
+        Z-level fields: zf_ptrs[3 * s + k] = source s (0 cT, 1 c) at order k."""
+        if len(zf_ptrs) != 6:
+            raise ValueError("six Z-level fields are required")
+        d = _desc(slab_shape_zyx, spacing)
+        self._chk(self._lib.ife_stage_jet_features(
+            self._h, _ptr_array(zf_ptrs), C.c_void_p(mask_ptr or 0), mask_dtype, C.byref(d), float(sigma),
+            C.c_void_p(out_ptr), layout))
+
     def stage_recursive_gaussian_quotient(self, num_ptrs, den_ptrs, out_ptrs, shape_zyx, spacing,
                                           axis_xyz, sigmas):
         """Last axis pass in its quotient form: out[j] = G(num[j]) / G(den[j]) (<= 4 jobs)."""
@@ -883,30 +939,24 @@ class Multi:
     def set_option(self, option, value):
         self._chk(self._lib.ife_multi_set_option(self._h, int(option), int(value)))
 
-    def emphysema_features(self, image, mask, sigmas, spacing=(1.0, 1.0, 1.0), layout=INTERLEAVED):
+    def _features(self, call, image, mask, sigmas, spacing, layout):
         image, idt = _image_arg(image)
         mask, mdt, mptr = _mask_arg(mask)
         d = _desc(image.shape, spacing)
         sig = _sigma_arg(sigmas)
         shp = image.shape + (8,) if layout == INTERLEAVED else (8,) + image.shape
         out = np.empty((len(sigmas),) + shp, np.float32)
-        self._chk(self._lib.ife_multi_emphysema_features(
-            self._h, image.ctypes.data, idt, mptr, mdt, C.byref(d), sig,
-            len(sigmas), out.ctypes.data, layout))
+        self._chk(call(self._h, image.ctypes.data, idt, mptr, mdt, C.byref(d), sig,
+                       len(sigmas), out.ctypes.data, layout))
         return out
 
-
-    def emphysema_features_stream(self, image, mask, sigmas, spacing=(1.0, 1.0, 1.0), layout=INTERLEAVED):
-        """Generator over the scales: one upload and prepass, every scale enqueued on every
-        device, then one blocking fetch per scale (ife_multi_emphysema_features_begin / _fetch /
-        _end) -- the scale loop of tools/ExtractFeatures.cxx:132-154 over several devices."""
+    def _features_stream(self, begin, image, mask, sigmas, spacing, layout):
         image, idt = _image_arg(image)
         mask, mdt, mptr = _mask_arg(mask)
         d = _desc(image.shape, spacing)
         sig = _sigma_arg(sigmas)
         shp = image.shape + (8,) if layout == INTERLEAVED else (8,) + image.shape
-        self._chk(self._lib.ife_multi_emphysema_features_begin(
-            self._h, image.ctypes.data, idt, mptr, mdt, C.byref(d), sig, len(sigmas), layout))
+        self._chk(begin(self._h, image.ctypes.data, idt, mptr, mdt, C.byref(d), sig, len(sigmas), layout))
         try:
             for k in range(len(sigmas)):
                 out = np.empty(shp, np.float32)
@@ -914,6 +964,25 @@ class Multi:
                 yield out
         finally:
             self._chk(self._lib.ife_multi_emphysema_features_end(self._h))
+
+    def emphysema_features(self, image, mask, sigmas, spacing=(1.0, 1.0, 1.0), layout=INTERLEAVED):
+        return self._features(self._lib.ife_multi_emphysema_features, image, mask, sigmas, spacing, layout)
+
+    def emphysema_features_stream(self, image, mask, sigmas, spacing=(1.0, 1.0, 1.0), layout=INTERLEAVED):
+        """Generator over the scales: one upload and prepass, every scale enqueued on every
+        device, then one blocking fetch per scale (ife_multi_emphysema_features_begin / _fetch /
+        _end) -- the scale loop of tools/ExtractFeatures.cxx:132-154 over several devices."""
+        return self._features_stream(self._lib.ife_multi_emphysema_features_begin, image, mask, sigmas, spacing,
+                                     layout)
+
+    def differential_features(self, image, mask, sigmas, spacing=(1.0, 1.0, 1.0), layout=INTERLEAVED):
+        """Context.differential_features over the devices of the engine (bit for bit)."""
+        return self._features(self._lib.ife_multi_differential_features, image, mask, sigmas, spacing, layout)
+
+    def differential_features_stream(self, image, mask, sigmas, spacing=(1.0, 1.0, 1.0), layout=INTERLEAVED):
+        """emphysema_features_stream with every scale that of differential_features."""
+        return self._features_stream(self._lib.ife_multi_differential_features_begin, image, mask, sigmas,
+                                     spacing, layout)
 
 
 class Samples:

@@ -88,35 +88,40 @@ struct JetLaunch {
   }
 };
 
-// The twenty fields of one scale from cT and c (device, float).  On return f points into the
-// workspace; every other slot is free again.
-int jet_fields(ife_ctx *ctx, const float *ct, const float *c, const ife_volume_desc *vol, double sigma,
-               JetFields *f) {
+// The Z-level fields of one scale: order k of source s (0 = cT, 1 = c), a slot of the workspace
+// or (slot < 0) a field of the caller's (ife_stage_jet_features: the Z level of a Z-slab is made
+// by the slab kernels).
+struct JetZ {
+  const float *p[2][3];
+  int slot[2][3];
+};
+
+// The workspace of one scale for this volume, every slot free.
+int jet_workspace(ife_ctx *ctx, const ife_volume_desc *vol, JetSlots *sl) {
   const size_t n = (size_t)(vol->nx * vol->ny * vol->nz);
-  JetSlots sl;
-  sl.pitch = (n + 3) / 4 * 4;
-  int rc = ensure(ctx, ctx->dj_ws, (size_t)JET_SLOTS * sl.pitch * sizeof(float));
+  sl->pitch = (n + 3) / 4 * 4;
+  int rc = ensure(ctx, ctx->dj_ws, (size_t)JET_SLOTS * sl->pitch * sizeof(float));
   if (rc) return rc;
-  sl.base = (float *)ctx->dj_ws.p;
-  for (int s = 0; s < JET_SLOTS; ++s) { sl.used[s] = false; sl.readers[s] = 0; }
-  const float *src[2] = {ct, c};
-  const char *bad = "the slot schedule of the differential convolution does not fit its workspace";
-  // z level: order k of source s, read by 3 - k jobs of the x level
-  int zs[2][3];
-  {
-    JetLaunch L(ctx, vol, &sl, sigma, 2);
-    for (int s = 0; s < 2; ++s)
-      for (int k = 0; k < 3; ++k)
-        if ((zs[s][k] = L.add(src[s], -1, k, 3 - k)) < 0) return fail(ctx, IFE_E_STATE, "%s", bad);
-    if ((rc = L.run())) return rc;
-  }
+  sl->base = (float *)ctx->dj_ws.p;
+  for (int s = 0; s < JET_SLOTS; ++s) { sl->used[s] = false; sl->readers[s] = 0; }
+  return IFE_OK;
+}
+
+const char *const kJetBadSchedule = "the slot schedule of the differential convolution does not fit its workspace";
+
+// The X and Y levels behind the Z level: the twenty fields of one scale from its six Z-level
+// fields.  On return f points into the workspace; every other slot is free again.
+int jet_fields_xy(ife_ctx *ctx, JetSlots &sl, const JetZ &z, const ife_volume_desc *vol, double sigma,
+                  JetFields *f) {
+  int rc;
   // x level, one launch per source: xs[s][ox][oz], read by 3 - ox - oz jobs of the y level
   int xs[2][3][3];
   for (int s = 0; s < 2; ++s) {
     JetLaunch L(ctx, vol, &sl, sigma, 0);
     for (int oz = 0; oz < 3; ++oz)
       for (int ox = 0; ox + oz < 3; ++ox)
-        if ((xs[s][ox][oz] = L.add(nullptr, zs[s][oz], ox, 3 - ox - oz)) < 0) return fail(ctx, IFE_E_STATE, "%s", bad);
+        if ((xs[s][ox][oz] = L.add(z.p[s][oz], z.slot[s][oz], ox, 3 - ox - oz)) < 0)
+          return fail(ctx, IFE_E_STATE, "%s", kJetBadSchedule);
     if ((rc = L.run())) return rc;
   }
   // y level: the jobs in the order that frees x-level fields soonest, cut into launches of eight
@@ -132,12 +137,32 @@ int jet_fields(ife_ctx *ctx, const float *ct, const float *c, const ife_volume_d
     for (int j = j0; j < std::min(20, j0 + IIR_MAX_JOBS); ++j) {
       const YJob &y = yjobs[j];
       const int o = L.add(nullptr, xs[y.s][y.ox][y.oz], y.oy, 1 << 20 /* the jet kernel: never given back */);
-      if (o < 0) return fail(ctx, IFE_E_STATE, "%s", bad);
+      if (o < 0) return fail(ctx, IFE_E_STATE, "%s", kJetBadSchedule);
       (y.s == 0 ? f->n : f->d)[jet_index(y.ox, y.oy, y.oz)] = sl.at(o);
     }
     if ((rc = L.run())) return rc;
   }
   return IFE_OK;
+}
+
+// The twenty fields of one scale from cT and c (device, float).  On return f points into the
+// workspace; every other slot is free again.
+int jet_fields(ife_ctx *ctx, const float *ct, const float *c, const ife_volume_desc *vol, double sigma,
+               JetFields *f) {
+  JetSlots sl;
+  int rc = jet_workspace(ctx, vol, &sl);
+  if (rc) return rc;
+  const float *src[2] = {ct, c};
+  // z level: order k of source s, read by 3 - k jobs of the x level
+  JetZ z;
+  JetLaunch L(ctx, vol, &sl, sigma, 2);
+  for (int s = 0; s < 2; ++s)
+    for (int k = 0; k < 3; ++k) {
+      if ((z.slot[s][k] = L.add(src[s], -1, k, 3 - k)) < 0) return fail(ctx, IFE_E_STATE, "%s", kJetBadSchedule);
+      z.p[s][k] = nullptr;
+    }
+  if ((rc = L.run())) return rc;
+  return jet_fields_xy(ctx, sl, z, vol, sigma, f);
 }
 
 // What the pointwise kernels need of the volume (pvec is launch_jet's own).
@@ -273,6 +298,35 @@ int ife_normalized_convolution_jet(ife_ctx *ctx, const float *image, const float
   if ((rc = jet_fields(ctx, tc, (const float *)dC, vol, sigma, &f))) return rc;
   if ((rc = launch_jet<JET_JET10>(ctx, f, (const uint8_t *)nullptr, (float *)dO, vol, layout))) return rc;
   return stage_out_end(ctx, mem, out10, n * 40);
+}
+
+
+int ife_stage_jet_features(ife_ctx *ctx, const float *const zf[6], const void *mask, int mask_dtype,
+                           const ife_volume_desc *slab, double sigma, float *out, int layout) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_vol(ctx, slab, false))) return rc;
+  if ((rc = check_layout_mem(ctx, layout, IFE_MEM_DEVICE))) return rc;
+  if (!zf || !out) return fail(ctx, IFE_E_ARG, "null pointer");
+  if ((rc = check_mask_dtype(ctx, mask, mask_dtype, true))) return rc;
+  if ((rc = check_sigma(ctx, sigma))) return rc;
+  if ((rc = check_axis_len(ctx, slab, 0)) || (rc = check_axis_len(ctx, slab, 1))) return rc;
+  if ((rc = check_in_alignment(ctx, mask, mask && mask_dtype == IFE_U16 ? 2 : 1, nullptr, 1))) return rc;
+  if ((rc = check_out_alignment(ctx, out, IFE_NUM_FEATURES, layout))) return rc;
+  JetZ z;
+  for (int s = 0; s < 2; ++s)
+    for (int k = 0; k < 3; ++k) {
+      if (!zf[3 * s + k]) return fail(ctx, IFE_E_ARG, "null pointer");
+      z.p[s][k] = zf[3 * s + k];
+      z.slot[s][k] = -1;
+    }
+  JetSlots sl;
+  if ((rc = jet_workspace(ctx, slab, &sl))) return rc;
+  JetFields f;
+  if ((rc = jet_fields_xy(ctx, sl, z, slab, sigma, &f))) return rc;
+  return with_mask_type(mask != nullptr, mask_dtype, mask, [&](auto msk) {
+    return launch_jet<JET_FEATURES8>(ctx, f, msk, out, slab, layout);
+  });
 }
 
 }  // extern "C"

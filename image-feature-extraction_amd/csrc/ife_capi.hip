@@ -51,6 +51,8 @@ namespace {
     template <int K, int S, typename TI, typename TM> static constexpr auto sweep_z = NS::iir_sweep_z_kernel<K, S, TI, TM>; \
     template <int K> static constexpr auto zslab_causal = NS::zslab_causal_kernel<K>;            \
     template <int K> static constexpr auto zslab_anti = NS::zslab_anti_kernel<K>;                \
+    template <int K> static constexpr auto zslab_causal3 = NS::zslab_causal3_kernel<K>;          \
+    template <int K> static constexpr auto zslab_anti3 = NS::zslab_anti3_kernel<K>;              \
     template <int K, int DIR> static constexpr auto zslab_fused = NS::zslab_fused_kernel<K, DIR>; \
     template <int K> static constexpr auto zslab_combine = NS::zslab_combine_kernel<K>;          \
   }
@@ -665,11 +667,18 @@ size_t zslab_ck_bytes(const ife_volume_desc *v) {
   return (size_t)zslab_pairs(v->nz) * 4 * L * 2 * sizeof(double);
 }
 // phase 0: causal sweep, 1: anticausal sweep, 2: combine, 3 / 4: fused with the causal /
-// anticausal recursion carried through the slab (zslab_fused_kernel)
+// anticausal recursion carried through the slab (zslab_fused_kernel).  orders: per job 0, 1 or 2
+// (null: all zero).  A lean sweep (phase 0 / 1) runs every three consecutive jobs with the same
+// input, the same sigma and the orders 0, 1, 2 through the shared-read kernels (zslab_causal3 /
+// zslab_anti3_kernel: one load per plane for the three), every other job through the per-job one.
 int launch_zslab(ife_ctx *ctx, int phase, int njobs, const float *const *in, float *const *out,
                  const ife_volume_desc *v, int64_t line0, int64_t nlines, const double *sigmas,
-                 int has_lo, int has_hi, const void *state_in, void *state_out, void *const *ck) {
+                 int has_lo, int has_hi, const void *state_in, void *state_out, void *const *ck,
+                 const int *orders = nullptr) {
   if (njobs < 1 || njobs > IIR_MAX_JOBS) return fail(ctx, IFE_E_ARG, "bad job count %d", njobs);
+  for (int j = 0; orders && j < njobs; ++j)
+    if (orders[j] < 0 || orders[j] > 2)
+      return fail(ctx, IFE_E_ARG, "the order of the recursive Gaussian must be 0, 1 or 2");
   const int64_t L = v->nx * v->ny, n = v->nz;
   if (line0 < 0 || nlines < 1 || line0 + nlines > L)
     return fail(ctx, IFE_E_ARG, "line range [%lld, %lld) outside the %lld lines of the slab",
@@ -684,10 +693,17 @@ int launch_zslab(ife_ctx *ctx, int phase, int njobs, const float *const *in, flo
   if ((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) % 8)
     return fail(ctx, IFE_E_ARG, "state buffers must be aligned to 8 bytes");
   const int64_t np = zslab_pairs(n);
-  ZSlabJobs jobs;
+  ZSlabJobs jobs, jobs3;  // per job; three by three for the shared-read sweeps
   memset(&jobs, 0, sizeof jobs);
+  memset(&jobs3, 0, sizeof jobs3);
+  int n1 = 0, n3 = 0, left3 = 0;  // jobs of `jobs`, sources of `jobs3`, jobs still to join the open three
   for (int j = 0; j < njobs; ++j) {
-    ZSlabJob &J = jobs.j[j];
+    if (left3 == 0 && phase < 2 && orders && j + 2 < njobs && in[j] == in[j + 1] && in[j] == in[j + 2] &&
+        sigmas[j] == sigmas[j + 1] && sigmas[j] == sigmas[j + 2] && orders[j] == 0 && orders[j + 1] == 1 &&
+        orders[j + 2] == 2)
+      left3 = 3;
+    ZSlabJob &J = left3 > 0 ? jobs3.j[3 * n3 + (3 - left3)] : jobs.j[n1++];
+    if (left3 > 0 && --left3 == 0) ++n3;
     if (!in[j] || !ck[j] || (phase >= 2 && (!out || !out[j] || out[j] == in[j])))
       return fail(ctx, IFE_E_ARG, "bad job buffers");
     if (reinterpret_cast<uintptr_t>(ck[j]) % 8 || reinterpret_cast<uintptr_t>(in[j]) % 4)
@@ -700,24 +716,37 @@ int launch_zslab(ife_ctx *ctx, int phase, int njobs, const float *const *in, flo
     const size_t rec = (size_t)nlines * IFE_Z_STATE_BYTES;  // [4][nlines] doubles per job
     if (state_in) J.sin_y = (const double *)((const char *)state_in + (size_t)j * rec);
     if (state_out) J.sout_y = (double *)((char *)state_out + (size_t)j * rec);
-    if (!(sigmas[j] > 0.0) || gauss_coeffs_order(sigmas[j], v->sz, 0, &J.c))
+    if (!(sigmas[j] > 0.0) || gauss_coeffs_order(sigmas[j], v->sz, orders ? orders[j] : 0, &J.c))
       return fail(ctx, IFE_E_ARG, "bad sigma or spacing");
   }
+  // the shared-read kernels keep one set of feedback coefficients: they are a function of sigma
+  // and spacing alone (gauss_coeffs_order)
+  for (int t = 0; t < n3; ++t)
+    for (int k = 1; k < 3; ++k)
+      if (memcmp(&jobs3.j[3 * t].c.D1, &jobs3.j[3 * t + k].c.D1, 4 * sizeof(double)))
+        return fail(ctx, IFE_E_STATE, "the feedback coefficients of one sigma differ between the orders");
   ZSlabGeom g;
   g.n = n; g.nlines = nlines; g.sstride = L; g.ck_stride = L;
   g.has_lo = has_lo ? 1 : 0; g.has_hi = has_hi ? 1 : 0;
-  g.njobs = njobs;
   g.ngroups = (int32_t)((nlines + 255) / 256);
-  const dim3 grid((unsigned)((g.ngroups + 7) / 8 * 8 * njobs), 1, 1);
   ProfScope ps(ctx, phase >= 2 ? KK_ZSLAB_COMBINE : KK_ZSLAB_SWEEP);
   with_iir_kernels(ctx->iir_fma, [&](auto ks) {
     using KS = decltype(ks);
-    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, jobs, g); };
-    if (phase == 0) launch(KS::template zslab_causal<ZSLAB_K>);
-    else if (phase == 1) launch(KS::template zslab_anti<ZSLAB_K>);
-    else if (phase == 3) launch(KS::template zslab_fused<ZSLAB_K, 0>);
-    else if (phase == 4) launch(KS::template zslab_fused<ZSLAB_K, 1>);
-    else launch(KS::template zslab_combine<ZSLAB_K>);
+    auto launch = [&](auto kernel, const ZSlabJobs &js, int nj) {  // nj: what iir_block_of deals out
+      if (nj == 0) return;
+      g.njobs = nj;
+      const dim3 grid((unsigned)((g.ngroups + 7) / 8 * 8 * nj), 1, 1);
+      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, js, g);
+    };
+    if (phase == 0) {
+      launch(KS::template zslab_causal3<ZSLAB_K>, jobs3, n3);
+      launch(KS::template zslab_causal<ZSLAB_K>, jobs, n1);
+    } else if (phase == 1) {
+      launch(KS::template zslab_anti3<ZSLAB_K>, jobs3, n3);
+      launch(KS::template zslab_anti<ZSLAB_K>, jobs, n1);
+    } else if (phase == 3) launch(KS::template zslab_fused<ZSLAB_K, 0>, jobs, n1);
+    else if (phase == 4) launch(KS::template zslab_fused<ZSLAB_K, 1>, jobs, n1);
+    else launch(KS::template zslab_combine<ZSLAB_K>, jobs, n1);
   });
   IFE_HIP(ctx, hipGetLastError());
   return IFE_OK;
@@ -1395,39 +1424,62 @@ size_t ife_stage_z_ck_bytes(const ife_volume_desc *slab) {
   return zslab_ck_bytes(slab);
 }
 
-int ife_stage_z_sweep(ife_ctx *ctx, int direction, int njobs, const float *const *in,
-                      const ife_volume_desc *slab, int64_t line0, int64_t nlines,
-                      const double *sigmas, int has_neighbour, const void *state_in,
-                      void *state_out, void *const *ck) {
+int ife_stage_z_sweep_order(ife_ctx *ctx, int direction, int njobs, const float *const *in,
+                            const ife_volume_desc *slab, int64_t line0, int64_t nlines,
+                            const double *sigmas, const int *orders, int has_neighbour,
+                            const void *state_in, void *state_out, void *const *ck) {
   int rc = bind(ctx);
   if (rc) return rc;
   if ((rc = check_vol(ctx, slab, false))) return rc;
   if (direction != 0 && direction != 1) return fail(ctx, IFE_E_ARG, "direction must be 0 (causal) or 1 (anticausal)");
   return launch_zslab(ctx, direction, njobs, in, nullptr, slab, line0, nlines, sigmas,
                       direction == 0 ? has_neighbour : 0, direction == 1 ? has_neighbour : 0, state_in,
-                      state_out, ck);
+                      state_out, ck, orders);
+}
+
+int ife_stage_z_sweep(ife_ctx *ctx, int direction, int njobs, const float *const *in,
+                      const ife_volume_desc *slab, int64_t line0, int64_t nlines,
+                      const double *sigmas, int has_neighbour, const void *state_in,
+                      void *state_out, void *const *ck) {
+  return ife_stage_z_sweep_order(ctx, direction, njobs, in, slab, line0, nlines, sigmas, nullptr, has_neighbour,
+                                 state_in, state_out, ck);
+}
+
+int ife_stage_z_combine_order(ife_ctx *ctx, int njobs, const float *const *in, float *const *out,
+                              const ife_volume_desc *slab, int64_t line0, int64_t nlines,
+                              const double *sigmas, const int *orders, int has_lo, int has_hi,
+                              void *const *ck) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_vol(ctx, slab, false))) return rc;
+  return launch_zslab(ctx, 2, njobs, in, out, slab, line0, nlines, sigmas, has_lo, has_hi, nullptr,
+                      nullptr, ck, orders);
 }
 
 int ife_stage_z_combine(ife_ctx *ctx, int njobs, const float *const *in, float *const *out,
                         const ife_volume_desc *slab, int64_t line0, int64_t nlines,
                         const double *sigmas, int has_lo, int has_hi, void *const *ck) {
+  return ife_stage_z_combine_order(ctx, njobs, in, out, slab, line0, nlines, sigmas, nullptr, has_lo, has_hi, ck);
+}
+
+int ife_stage_z_fused_order(ife_ctx *ctx, int direction, int njobs, const float *const *in,
+                            float *const *out, const ife_volume_desc *slab, int64_t line0, int64_t nlines,
+                            const double *sigmas, const int *orders, int has_lo, int has_hi,
+                            const void *state_in, void *state_out, void *const *ck) {
   int rc = bind(ctx);
   if (rc) return rc;
   if ((rc = check_vol(ctx, slab, false))) return rc;
-  return launch_zslab(ctx, 2, njobs, in, out, slab, line0, nlines, sigmas, has_lo, has_hi, nullptr,
-                      nullptr, ck);
+  if (direction != 0 && direction != 1) return fail(ctx, IFE_E_ARG, "direction must be 0 (causal) or 1 (anticausal)");
+  return launch_zslab(ctx, 3 + direction, njobs, in, out, slab, line0, nlines, sigmas, has_lo, has_hi,
+                      state_in, state_out, ck, orders);
 }
 
 int ife_stage_z_fused(ife_ctx *ctx, int direction, int njobs, const float *const *in,
                       float *const *out, const ife_volume_desc *slab, int64_t line0, int64_t nlines,
                       const double *sigmas, int has_lo, int has_hi, const void *state_in,
                       void *state_out, void *const *ck) {
-  int rc = bind(ctx);
-  if (rc) return rc;
-  if ((rc = check_vol(ctx, slab, false))) return rc;
-  if (direction != 0 && direction != 1) return fail(ctx, IFE_E_ARG, "direction must be 0 (causal) or 1 (anticausal)");
-  return launch_zslab(ctx, 3 + direction, njobs, in, out, slab, line0, nlines, sigmas, has_lo, has_hi,
-                      state_in, state_out, ck);
+  return ife_stage_z_fused_order(ctx, direction, njobs, in, out, slab, line0, nlines, sigmas, nullptr, has_lo,
+                                 has_hi, state_in, state_out, ck);
 }
 
 int ife_stage_recursive_gaussian_quotient(ife_ctx *ctx, int njobs, const float *const *num,

@@ -1765,6 +1765,283 @@ __global__ __launch_bounds__(256) void zslab_anti_kernel(ZSlabJobs jobs, ZSlabGe
   if (l.live) y4_store(J.sout_y, g.nlines, l.Lw, l.voff, a.y1, a.y2, a.y3, a.y4);
 }
 
+// ---- lean sweeps of three jobs over the same planes (orders 0, 1, 2 of one source) ----------
+// The differential path sweeps every source three times with one sigma: the jobs 3t, 3t + 1,
+// 3t + 2 of a launch read the same planes.  Here a lane owns one line of one SOURCE (g.njobs
+// counts sources): every register block is loaded once and advances the three recursions from
+// it -- the x history shared, three y histories, three sets of input coefficients, as
+// iir_sweep_z_kernel runs its scales side by side -- and the checkpoints and outgoing states of
+// the three jobs go exactly where zslab_causal_kernel / zslab_anti_kernel put them.  Every sample
+// sees the operations of the per-job kernels in their order: same bits.  The feedback
+// coefficients D1..D4 depend on sigma and spacing only, not on the order: the host sends three
+// jobs here only where theirs are the same doubles, and the steady loop keeps one set (32 scalar
+// registers of coefficients instead of 48).
+// Every memory operation of the pair loop is unconditional.  A block that does not exist is
+// replaced by the nearest one that does (its values are not used), rows past the slab's last
+// plane repeat that plane, and a lane past the last line computes on the last line; it never
+// stores, because every row of a record goes through a descriptor that ends with the launch's
+// last line.
+struct Sweep4 {
+  double k0, k1, k2, k3;  // N0..N3 (causal), M1..M4 (anticausal), D1..D4
+};
+// the four border coefficients of a slab job (first = 12: BN1..BN4, 16: BM1..BM4), re-read from
+// the kernel-argument segment where a border block needs them (edge_coefs, for ZSlabJobs as the
+// first argument); the other eight it needs are the steady loop's own
+__device__ __forceinline__ Sweep4 slab_border_coefs(uint32_t job, int first) {
+  typedef __attribute__((address_space(4))) const char kchar;
+  kchar *ka = (kchar *)__builtin_amdgcn_kernarg_segment_ptr() + (size_t)job * sizeof(ZSlabJob) + offsetof(ZSlabJob, c);
+  asm volatile("" : "+s"(ka));
+  typedef __attribute__((address_space(4))) const double kdouble;
+  kdouble *d = (kdouble *)ka + first;
+  return Sweep4{d[0], d[1], d[2], d[3]};
+}
+static_assert(offsetof(IirCoef, BN1) == 12 * sizeof(double) && offsetof(IirCoef, BM1) == 16 * sizeof(double),
+              "slab_border_coefs reads IirCoef as 20 doubles");
+// causal_step / anti_step with the x history outside the state
+__device__ __forceinline__ void sweep3_causal(SweepY &s, double x1, double x2, double x3, double xin,
+                                              const Sweep4 &N, const Sweep4 &D) {
+  const double a = IFE_MADD(x3, N.k3, IFE_MADD(x2, N.k2, IFE_MADD(x1, N.k1, xin * N.k0)));
+  const double t = IFE_MADD(s.y4, D.k3, IFE_MADD(s.y3, D.k2, IFE_MADD(s.y2, D.k1, s.y1 * D.k0)));
+  const double y = a - t;
+  s.y4 = s.y3; s.y3 = s.y2; s.y2 = s.y1; s.y1 = y;
+}
+__device__ __forceinline__ void sweep3_anti(SweepY &s, double x1, double x2, double x3, double x4,
+                                            const Sweep4 &M, const Sweep4 &D) {
+  const double a = IFE_MADD(x4, M.k3, IFE_MADD(x3, M.k2, IFE_MADD(x2, M.k1, x1 * M.k0)));
+  const double t = IFE_MADD(s.y4, D.k3, IFE_MADD(s.y3, D.k2, IFE_MADD(s.y2, D.k1, s.y1 * D.k0)));
+  const double y = a - t;
+  s.y4 = s.y3; s.y3 = s.y2; s.y2 = s.y1; s.y1 = y;
+}
+// causal_step_edge / anti_step_edge likewise: B are the border coefficients, i (n) as there
+__device__ __forceinline__ void sweep3_causal_edge(SweepY &s, double x1, double x2, double x3, double xin,
+                                                   const Sweep4 &N, const Sweep4 &D, const Sweep4 &B, int64_t i) {
+  const double d1 = i < 1 ? B.k0 : D.k0;
+  const double d2 = i < 2 ? B.k1 : D.k1;
+  const double d3 = i < 3 ? B.k2 : D.k2;
+  const double d4 = i < 4 ? B.k3 : D.k3;
+  const double a = IFE_MADD(x3, N.k3, IFE_MADD(x2, N.k2, IFE_MADD(x1, N.k1, xin * N.k0)));
+  const double t = IFE_MADD(s.y4, d4, IFE_MADD(s.y3, d3, IFE_MADD(s.y2, d2, s.y1 * d1)));
+  const double y = a - t;
+  s.y4 = s.y3; s.y3 = s.y2; s.y2 = s.y1; s.y1 = y;
+}
+__device__ __forceinline__ void sweep3_anti_edge(SweepY &s, double x1, double x2, double x3, double x4,
+                                                 const Sweep4 &M, const Sweep4 &D, const Sweep4 &B, int64_t i,
+                                                 int64_t n) {
+  const double d1 = i + 1 >= n ? B.k0 : D.k0;
+  const double d2 = i + 2 >= n ? B.k1 : D.k1;
+  const double d3 = i + 3 >= n ? B.k2 : D.k2;
+  const double d4 = i + 4 >= n ? B.k3 : D.k3;
+  const double a = IFE_MADD(x4, M.k3, IFE_MADD(x3, M.k2, IFE_MADD(x2, M.k1, x1 * M.k0)));
+  const double t = IFE_MADD(s.y4, d4, IFE_MADD(s.y3, d3, IFE_MADD(s.y2, d2, s.y1 * d1)));
+  const double y = a - t;
+  s.y4 = s.y3; s.y3 = s.y2; s.y2 = s.y1; s.y1 = y;
+}
+// K samples from plane i0 (0 <= i0 < n) of the lane's line, rows past the slab's last plane
+// repeating it: slab_load_block without its branch (the row offsets are scalar minima)
+template <int K>
+__device__ __forceinline__ void slab_load_block_clamped(const float *in, const ZSlabGeom &g, int64_t Lw,
+                                                        uint32_t voff, int64_t i0, float (&x)[K]) {
+  const rsrc_t r = IFE_IN_RSRC(in + Lw + i0 * g.sstride);
+  const uint32_t sst = (uint32_t)g.sstride;
+  const int64_t left = g.n - 1 - i0;
+  const uint32_t lastj = (uint32_t)(left < K - 1 ? left : K - 1);
+#pragma unroll
+  for (int j = 0; j < K; ++j)
+    x[j] = buf_ld_f32(r, voff * 4u, ((uint32_t)j < lastj ? (uint32_t)j : lastj) * sst * 4u);
+}
+// One record [4][stride] of a live lane; `live_bytes` = 8 * (lines of this wave inside the
+// launch): the lanes past them fall outside every row's descriptor and their stores are dropped
+__device__ __forceinline__ void y4_store_live(double *y, int64_t stride, int64_t Lw, uint32_t lane,
+                                              uint32_t live_bytes, const SweepY &s) {
+  double *const base = reinterpret_cast<double *>(uniform64(reinterpret_cast<int64_t>(y))) + Lw;
+  buf_st_f64(make_rsrc_range(base, live_bytes), lane * 8u, 0u, s.y1);
+  buf_st_f64(make_rsrc_range(base + stride, live_bytes), lane * 8u, 0u, s.y2);
+  buf_st_f64(make_rsrc_range(base + 2 * stride, live_bytes), lane * 8u, 0u, s.y3);
+  buf_st_f64(make_rsrc_range(base + 3 * stride, live_bytes), lane * 8u, 0u, s.y4);
+}
+
+// (three waves per SIMD: held to four, the three chains spill to scratch inside the steady block
+// and the sweep of a 512 x 512 x 64 slab takes 0.093 ms instead of 0.082)
+template <int K>
+__global__ __launch_bounds__(256) void zslab_causal3_kernel(ZSlabJobs jobs, ZSlabGeom g) {
+  const IirBlock blk = slab_block_of(g, blockIdx.x);  // g.njobs = sources: blk.job is the source
+  if (!blk.live) return;
+  SlabLine l;
+  if (!slab_line(g, blk.group, l)) return;
+  const uint32_t j0 = blk.job * 3u;
+  const int64_t n = g.n;
+  const int64_t nb = (n + K - 1) / K;
+  const int64_t np = (nb + 1) / 2;
+  const int64_t ioff = g.has_lo ? 4 : 0;
+  const int64_t rest = g.nlines - l.Lw;  // >= 1 (slab_line)
+  const uint32_t live_bytes = (uint32_t)(rest < 64 ? rest : 64) * 8u;
+  const float *const in = jobs.j[j0].in;  // the three jobs read the same planes (the host's test)
+  Sweep4 N[3];
+  double *cy[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const ZSlabJob &J = jobs.j[j0 + k];
+    N[k] = Sweep4{J.c.N0, J.c.N1, J.c.N2, J.c.N3};
+    cy[k] = J.cy;
+  }
+  const Sweep4 D = {jobs.j[j0].c.D1, jobs.j[j0].c.D2, jobs.j[j0].c.D3, jobs.j[j0].c.D4};
+  SweepY s[3];
+  double x1, x2, x3;
+  float xb[K], xn[K];
+  slab_load_block_clamped<K>(in, g, l.Lw, l.voff, 0, xb);
+  if (g.has_lo) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      y4_load(jobs.j[j0 + k].sin_y, g.nlines, l.Lw, l.voff, s[k].y1, s[k].y2, s[k].y3, s[k].y4);
+    float h[3];  // x[-3], x[-2], x[-1]: the last planes of the slab below
+    slab_load_planes<3>(in, g, l.Lw, l.voff, -3, h);
+    x1 = (double)h[2]; x2 = (double)h[1]; x3 = (double)h[0];
+  } else {
+    const double e0 = (double)xb[0];
+    x1 = x2 = x3 = e0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s[k] = SweepY{e0, e0, e0, e0};
+  }
+  // the recursions over the block in xb, which starts at plane i0 (uniform branches over
+  // arithmetic only).  The border form where zslab_causal_kernel takes it, one job after the
+  // other, each with its border coefficients and its own copy of the x history.
+  auto run = [&](int64_t i0, bool first) {
+    if (i0 + K <= n && !first) {
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        // (scheduling fence: left alone, the conversions of the whole block move to its front)
+        if (j % IFE_IIR_FENCE == 0) __builtin_amdgcn_sched_barrier(0);
+        const double xin = (double)xb[j];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sweep3_causal(s[k], x1, x2, x3, xin, N[k], D);
+        x3 = x2; x2 = x1; x1 = xin;
+      }
+    } else {
+      double e1 = x1, e2 = x2, e3 = x3;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const Sweep4 B = slab_border_coefs(j0 + (uint32_t)k, 12);
+        e1 = x1; e2 = x2; e3 = x3;
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+          if (i0 + j < n) {
+            const double xin = (double)xb[j];
+            sweep3_causal_edge(s[k], e1, e2, e3, xin, N[k], D, B, i0 + j + ioff);
+            e3 = e2; e2 = e1; e1 = xin;
+          }
+      }
+      x1 = e1; x2 = e2; x3 = e3;
+    }
+  };
+  for (int64_t p = 0; p < np; ++p) {
+    const int64_t iA = 2 * p * K, iB = iA + K;
+    const bool hasB = iB < n;
+    const int64_t iBe = hasB ? iB : iA;  // the pair's last block that exists
+    slab_load_block_clamped<K>(in, g, l.Lw, l.voff, iBe, xn);
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      y4_store_live(cy[k] + p * 4 * g.ck_stride, g.ck_stride, l.Lw, l.lane, live_bytes, s[k]);
+    run(iA, p == 0 && !g.has_lo);
+#pragma unroll
+    for (int j = 0; j < K; ++j) xb[j] = xn[j];
+    slab_load_block_clamped<K>(in, g, l.Lw, l.voff, iB + K < n ? iB + K : iBe, xn);
+    if (hasB) run(iB, false);
+#pragma unroll
+    for (int j = 0; j < K; ++j) xb[j] = xn[j];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) y4_store_live(jobs.j[j0 + k].sout_y, g.nlines, l.Lw, l.lane, live_bytes, s[k]);
+}
+
+// (four waves per SIMD, without scratch in the exact build: two sources of a 512 x 512 slab are
+// eight waves per SIMD, two full rounds)
+template <int K>
+__global__ __launch_bounds__(256, 4) void zslab_anti3_kernel(ZSlabJobs jobs, ZSlabGeom g) {
+  const IirBlock blk = slab_block_of(g, blockIdx.x);  // g.njobs = sources: blk.job is the source
+  if (!blk.live) return;
+  SlabLine l;
+  if (!slab_line(g, blk.group, l)) return;
+  const uint32_t j0 = blk.job * 3u;
+  const int64_t n = g.n;
+  const int64_t nb = (n + K - 1) / K;
+  const int64_t np = (nb + 1) / 2;
+  const int64_t nedge = g.has_hi ? n + 8 : n;
+  const int64_t rest = g.nlines - l.Lw;  // >= 1 (slab_line)
+  const uint32_t live_bytes = (uint32_t)(rest < 64 ? rest : 64) * 8u;
+  const float *const in = jobs.j[j0].in;
+  Sweep4 M[3];
+  double *ay[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const ZSlabJob &J = jobs.j[j0 + k];
+    M[k] = Sweep4{J.c.M1, J.c.M2, J.c.M3, J.c.M4};
+    ay[k] = J.ay;
+  }
+  const Sweep4 D = {jobs.j[j0].c.D1, jobs.j[j0].c.D2, jobs.j[j0].c.D3, jobs.j[j0].c.D4};
+  SweepY a[3];
+  double x1, x2, x3, x4;
+  float xb[K], xn[K];
+  slab_load_block_clamped<K>(in, g, l.Lw, l.voff, (nb - 1) * K, xb);
+  if (g.has_hi) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      y4_load(jobs.j[j0 + k].sin_y, g.nlines, l.Lw, l.voff, a[k].y1, a[k].y2, a[k].y3, a[k].y4);
+    float h[4];  // x[n .. n+3]: the first planes of the slab above
+    slab_load_planes<4>(in, g, l.Lw, l.voff, n, h);
+    x1 = (double)h[0]; x2 = (double)h[1]; x3 = (double)h[2]; x4 = (double)h[3];
+  } else {
+    const double xN = (double)xb[K - 1];  // the clamped load repeats x[n-1]
+    x1 = x2 = x3 = x4 = xN;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a[k] = SweepY{xN, xN, xN, xN};
+  }
+  auto run = [&](int64_t i0) {
+    if (i0 + K + 4 <= nedge && i0 + K <= n) {
+#pragma unroll
+      for (int j = K - 1; j >= 0; --j) {
+        if (j % IFE_IIR_FENCE == 1) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sweep3_anti(a[k], x1, x2, x3, x4, M[k], D);
+        x4 = x3; x3 = x2; x2 = x1; x1 = (double)xb[j];
+      }
+    } else {
+      double e1 = x1, e2 = x2, e3 = x3, e4 = x4;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const Sweep4 B = slab_border_coefs(j0 + (uint32_t)k, 16);
+        e1 = x1; e2 = x2; e3 = x3; e4 = x4;
+#pragma unroll
+        for (int j = K - 1; j >= 0; --j)
+          if (i0 + j < n) {
+            sweep3_anti_edge(a[k], e1, e2, e3, e4, M[k], D, B, i0 + j, nedge);
+            e4 = e3; e3 = e2; e2 = e1; e1 = (double)xb[j];
+          }
+      }
+      x1 = e1; x2 = e2; x3 = e3; x4 = e4;
+    }
+  };
+  for (int64_t p = np - 1; p >= 0; --p) {
+    const int64_t iA = 2 * p * K, iB = iA + K;
+    const bool hasB = iB < n;  // false for the line's last pair at most
+    // xb holds the pair's last block that exists; its checkpoint lies in front of that block
+    slab_load_block_clamped<K>(in, g, l.Lw, l.voff, iA, xn);
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      y4_store_live(ay[k] + p * 4 * g.ck_stride, g.ck_stride, l.Lw, l.lane, live_bytes, a[k]);
+    if (hasB) {
+      run(iB);
+#pragma unroll
+      for (int j = 0; j < K; ++j) xb[j] = xn[j];
+    }
+    slab_load_block_clamped<K>(in, g, l.Lw, l.voff, p > 0 ? iA - K : iA, xn);
+    run(iA);
+#pragma unroll
+    for (int j = 0; j < K; ++j) xb[j] = xn[j];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) y4_store_live(jobs.j[j0 + k].sout_y, g.nlines, l.Lw, l.lane, live_bytes, a[k]);
+}
+
 // ---- combine: both recursions of every pair from its two checkpoints, summed and stored ----
 template <int K>
 __global__ __launch_bounds__(256, 3) void zslab_combine_kernel(ZSlabJobs jobs, ZSlabGeom g) {

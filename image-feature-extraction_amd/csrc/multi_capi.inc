@@ -15,7 +15,9 @@
 // at rank r in step r + i, anticausal in step W-1-r + i), so no wait can refer to an event
 // that has not been recorded.  The same device may appear more than once in the list (that
 // is how the tests exercise W > 1 on a one-GPU box); the reference has no counterpart
-// (SURVEY.md section 8e).  Included by ife_capi.hip.
+// (SURVEY.md section 8e).  The differential path (ife_multi_differential_features) runs the same
+// slabs, uploads and state chains with six Z jobs per scale and nothing but slab-local work behind
+// them (multi_run, MultiPath).  Included by ife_capi.hip.
 
 namespace {
 
@@ -197,9 +199,19 @@ int ife_multi_set_option(ife_multi *m, int option, int value) {
 
 namespace {
 
-// Everything ife_multi_emphysema_features enqueues; may return early with work in flight and
-// events alive -- the caller drains (multi_drain) whatever this returns.
-int multi_run(ife_multi *m, const void *image, int image_dtype, const void *mask, int mask_dtype,
+// The feature path of a run.  Both cut the volume into the same slabs, upload them with the same
+// overlap and carry the Z recursion through the same two state chains; they differ in the Z jobs
+// of a scale and in what the bulk stream makes of the Z output:
+//   MULTI_FD   numerator and denominator (or the image alone), order 0; then X, Y with the
+//              quotient, one stencil plane from each neighbour, ife_stage_features;
+//   MULTI_JET  cT and c at orders 0, 1, 2, source-major (so that the lean sweeps read every plane
+//              once for its three orders); then ife_stage_jet_features, which is slab-local: no
+//              plane is exchanged.  c is the constant 1.0f without a mask, as jet_sources makes it.
+enum MultiPath { MULTI_FD, MULTI_JET };
+
+// Everything a feature call enqueues; may return early with work in flight and events alive --
+// the caller drains (multi_drain) whatever this returns.
+int multi_run(ife_multi *m, MultiPath path, const void *image, int image_dtype, const void *mask, int mask_dtype,
               const ife_volume_desc *vol, const float *sigmas, int n_sigmas, int layout) {
   if (!vol || !image || !sigmas) return mfail(m, IFE_E_ARG, "null pointer");
   const int W = (int)m->ranks.size();
@@ -215,7 +227,10 @@ int multi_run(ife_multi *m, const void *image, int image_dtype, const void *mask
                                 "(%lld x %lld x %lld over %d devices)",
                  (long long)nx, (long long)ny, (long long)nz, W);
   if ((rc = check_vol(c0, vol, false))) return mfail(m, rc, "%s", c0->err.c_str());  // spacing
+  const bool jet = path == MULTI_JET;
   const int nf = mask ? 2 : 1, S = n_sigmas;
+  const int nsrc = jet ? 2 : nf;  // float sources of the Z jobs
+  const int jps = jet ? 6 : nf;   // Z jobs per scale: job s * jps + k * (jps / nsrc) + order
   const int64_t plane = nx * ny;
   const size_t isz = dtype_size(image_dtype), msz = mask ? dtype_size(mask_dtype) : 0;
   // slabs: nz / W planes each, the remainder spread over the first ranks
@@ -230,7 +245,7 @@ int multi_run(ife_multi *m, const void *image, int image_dtype, const void *mask
     }
   }
   // chain items: (scale group, line group); groups as slab.py chooses them
-  const int max_jobs = IIR_MAX_JOBS / nf;
+  const int max_jobs = IIR_MAX_JOBS / jps;  // scales per chain item (one on the differential path)
   const int spi = std::max(1, std::min(max_jobs, S));
   std::vector<std::vector<int>> sgroups;
   for (int s0 = 0; s0 < S; s0 += spi) {
@@ -267,20 +282,22 @@ int multi_run(ife_multi *m, const void *image, int image_dtype, const void *mask
     ife_volume_desc slab = {nx, ny, R.nzl, vol->sx, vol->sy, vol->sz};
     int rc = mensure(m, R, R.img, nve * isz);
     if (!rc && mask) rc = mensure(m, R, R.mask, nve * msz);
-    for (int k = 0; k < nf && !rc; ++k) rc = mensure(m, R, R.src[k], nve * 4);
+    for (int k = 0; k < nsrc && !rc; ++k) rc = mensure(m, R, R.src[k], (nve + 3) / 4 * 16);  // whole 16-byte pieces
     if (!rc) rc = mensure(m, R, R.out, nvl * IFE_NUM_FEATURES * 4 * (size_t)S);
-    R.zo.resize((size_t)(S * nf)); R.xo.resize((size_t)(S * nf));
-    R.pad.resize((size_t)S); R.ck.resize((size_t)(S * nf));
-    for (int j = 0; j < S * nf && !rc; ++j) {
+    // (never shrunk: an engine that runs both paths in turn keeps the buffers of both)
+    R.zo.resize(std::max(R.zo.size(), (size_t)(S * jps))); R.xo.resize(std::max(R.xo.size(), (size_t)(S * nf)));
+    R.pad.resize(std::max(R.pad.size(), (size_t)S)); R.ck.resize(std::max(R.ck.size(), (size_t)(S * jps)));
+    for (int j = 0; j < S * jps && !rc; ++j) {
       rc = mensure(m, R, R.zo[(size_t)j], nvl * 4);
-      if (!rc) rc = mensure(m, R, R.xo[(size_t)j], nvl * 4);
       if (!rc) rc = mensure(m, R, R.ck[(size_t)j], ife_stage_z_ck_bytes(&slab));
     }
-    for (int j = 0; j < S && !rc; ++j)  // the smoothed value of a scale with one halo plane each side
+    for (int j = 0; j < S * nf && !rc && !jet; ++j) rc = mensure(m, R, R.xo[(size_t)j], nvl * 4);
+    for (int j = 0; j < S && !rc && !jet; ++j)  // the smoothed value of a scale with one halo plane each side
       rc = mensure(m, R, R.pad[(size_t)j], (size_t)((R.nzl + 2) * plane) * 4);
-    R.c_in.resize((size_t)NI); R.c_out.resize((size_t)NI); R.a_in.resize((size_t)NI); R.a_out.resize((size_t)NI);
+    const size_t ni = std::max(R.c_in.size(), (size_t)NI);
+    R.c_in.resize(ni); R.c_out.resize(ni); R.a_in.resize(ni); R.a_out.resize(ni);
     for (int i = 0; i < NI && !rc; ++i) {
-      const size_t sb = sgroups[(size_t)items[(size_t)i].q].size() * (size_t)nf * IFE_Z_STATE_BYTES *
+      const size_t sb = sgroups[(size_t)items[(size_t)i].q].size() * (size_t)jps * IFE_Z_STATE_BYTES *
                         (size_t)lgroups[(size_t)items[(size_t)i].g].second;
       rc = mensure(m, R, R.c_in[(size_t)i], sb);
       if (!rc) rc = mensure(m, R, R.c_out[(size_t)i], sb);
@@ -304,6 +321,13 @@ int multi_run(ife_multi *m, const void *image, int image_dtype, const void *mask
     ife_volume_desc ext = {nx, ny, R.lo + R.nzl + R.hi, vol->sx, vol->sy, vol->sz};  // the prepass covers the overlap
     IFE_MCTX(m, R, R.bulk, ife_stage_prepare(R.bulk, R.img.p, image_dtype, mask ? R.mask.p : nullptr, mask_dtype,
                                              &ext, 1, (float *)R.src[0].p, mask ? (float *)R.src[1].p : nullptr));
+    if (jet && !mask) {  // certainty one everywhere: the second source is the constant
+      const int64_t n4 = ((R.lo + R.nzl + R.hi) * plane + 3) / 4;
+      const unsigned blocks = (unsigned)std::min<int64_t>((n4 + 255) / 256, 0x7fffffff);
+      IFE_MHIP(m, hipSetDevice(R.dev));
+      hipLaunchKernelGGL(stream_fill_kernel, dim3(blocks), dim3(256), 0, R.sb, (float4 *)R.src[1].p, n4, 1.0f);
+      IFE_MHIP(m, hipGetLastError());
+    }
     int rc = mrecord(m, R, R.sb, &prepared[(size_t)r]);
     if (!rc) rc = mwait(m, R, R.sc, prepared[(size_t)r]);
     if (rc) return rc;
@@ -323,15 +347,20 @@ int multi_run(ife_multi *m, const void *image, int image_dtype, const void *mask
         const int64_t l0 = lgroups[(size_t)items[(size_t)i].g].first, nl = lgroups[(size_t)items[(size_t)i].g].second;
         const bool has_nb = d == 0 ? r > 0 : r < W - 1;
         const float *in[IIR_MAX_JOBS];
+        float *zo_w[IIR_MAX_JOBS];
         void *ck[IIR_MAX_JOBS];
         double sg[IIR_MAX_JOBS];
+        int ord[IIR_MAX_JOBS];
         int nj = 0;
         for (int s : ss)
-          for (int k = 0; k < nf; ++k, ++nj) {
-            in[nj] = (const float *)R.src[k].p + R.lo * plane;  // the slab's own plane 0
-            ck[nj] = R.ck[(size_t)(s * nf + k)].p;
+          for (int k = 0; k < jps; ++k, ++nj) {
+            in[nj] = (const float *)R.src[k / (jps / nsrc)].p + R.lo * plane;  // the slab's own plane 0
+            zo_w[nj] = (float *)R.zo[(size_t)(s * jps + k)].p;
+            ck[nj] = R.ck[(size_t)(s * jps + k)].p;
             sg[nj] = (double)sigmas[s];
+            ord[nj] = k % (jps / nsrc);
           }
+        const int *orders = jet ? ord : nullptr;
         int rc = has_nb ? mwait(m, R, R.sc, arrived[(size_t)d][(size_t)r][(size_t)i]) : IFE_OK;
         if (rc) return rc;
         DevBuf &sin = d == 0 ? R.c_in[(size_t)i] : R.a_in[(size_t)i];
@@ -340,15 +369,11 @@ int multi_run(ife_multi *m, const void *image, int image_dtype, const void *mask
         // carried through the slab together with the combine (slab.py, SlabEngine.lean)
         const int lean = r <= W - 1 - r ? 0 : 1;
         if (d == lean) {
-          IFE_MCTX(m, R, R.chain, ife_stage_z_sweep(R.chain, d, nj, in, &slab, l0, nl, sg, has_nb ? 1 : 0,
-                                                    has_nb ? sin.p : nullptr, sout.p, ck));
+          IFE_MCTX(m, R, R.chain, ife_stage_z_sweep_order(R.chain, d, nj, in, &slab, l0, nl, sg, orders, has_nb ? 1 : 0,
+                                                          has_nb ? sin.p : nullptr, sout.p, ck));
         } else {
-          float *zo_w[IIR_MAX_JOBS];
-          int j2 = 0;
-          for (int s : ss)
-            for (int k = 0; k < nf; ++k, ++j2) zo_w[j2] = (float *)R.zo[(size_t)(s * nf + k)].p;
-          IFE_MCTX(m, R, R.chain, ife_stage_z_fused(R.chain, d, nj, in, zo_w, &slab, l0, nl, sg, r > 0, r < W - 1,
-                                                    has_nb ? sin.p : nullptr, sout.p, ck));
+          IFE_MCTX(m, R, R.chain, ife_stage_z_fused_order(R.chain, d, nj, in, zo_w, &slab, l0, nl, sg, orders, r > 0,
+                                                          r < W - 1, has_nb ? sin.p : nullptr, sout.p, ck));
         }
         if ((rc = mrecord(m, R, R.sc, &swept[(size_t)d][(size_t)r][(size_t)i]))) return rc;
         const int nb = d == 0 ? r + 1 : r - 1;
@@ -365,6 +390,33 @@ int multi_run(ife_multi *m, const void *image, int image_dtype, const void *mask
   // ---- bulk: X, Y (quotient), stencil planes, features, per bulk group ------------------------
   const size_t pb = (size_t)plane * 4;
   m->s_done.assign((size_t)W, std::vector<hipEvent_t>((size_t)S, nullptr));
+  m->s_vol = *vol;
+  m->s_scales = S;
+  m->s_layout = layout;
+  if (jet) {
+    // ---- bulk of the differential path: per scale X level, Y level and the pointwise pass, all
+    // slab-local (a chain item holds one scale: scale group q is scale q) ----------------------
+    for (int s = 0; s < S; ++s)
+      for (int r = 0; r < W; ++r) {
+        MultiRank &R = m->ranks[(size_t)r];
+        ife_volume_desc slab = {nx, ny, R.nzl, vol->sx, vol->sy, vol->sz};
+        const int fat = r <= W - 1 - r ? 1 : 0;
+        for (int i = 0; i < NI; ++i)
+          if (items[(size_t)i].q == s) {
+            int rc = mwait(m, R, R.sb, swept[(size_t)fat][(size_t)r][(size_t)i]);  // the fused kernels wrote the Z output
+            if (rc) return rc;
+          }
+        const float *zf[6];
+        for (int k = 0; k < 6; ++k) zf[k] = (const float *)R.zo[(size_t)(s * 6 + k)].p;
+        const void *own_mask = mask ? (const char *)R.mask.p + (size_t)(R.lo * plane) * msz : nullptr;
+        const size_t scale_out = (size_t)(R.nzl * plane) * IFE_NUM_FEATURES;
+        IFE_MCTX(m, R, R.bulk, ife_stage_jet_features(R.bulk, zf, own_mask, mask_dtype, &slab, (double)sigmas[s],
+                                                      (float *)R.out.p + (size_t)s * scale_out, layout));
+        int rc = mrecord(m, R, R.sb, &m->s_done[(size_t)r][(size_t)s]);
+        if (rc) return rc;
+      }
+    return IFE_OK;
+  }
   for (const std::vector<int> &qs : bgroups) {
     std::vector<int> ss;
     for (int q : qs) for (int s : sgroups[(size_t)q]) ss.push_back(s);
@@ -438,9 +490,6 @@ int multi_run(ife_multi *m, const void *image, int image_dtype, const void *mask
       }
     }
   }
-  m->s_vol = *vol;
-  m->s_scales = S;
-  m->s_layout = layout;
   return IFE_OK;
 }
 
@@ -491,16 +540,13 @@ int multi_drain(ife_multi *m, bool failed) {
   return result;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ife_multi_emphysema_features(ife_multi *m, const void *image, int image_dtype, const void *mask,
-                                 int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
-                                 int n_sigmas, float *out, int layout) {
+// The blocking calls: every scale of `path` enqueued, fetched and drained.
+int multi_features(ife_multi *m, MultiPath path, const void *image, int image_dtype, const void *mask,
+                   int mask_dtype, const ife_volume_desc *vol, const float *sigmas, int n_sigmas, float *out,
+                   int layout) {
   if (!m) return IFE_E_ARG;
   if (m->streaming) return mfail(m, IFE_E_STATE, "a streaming call is in flight: ife_multi_emphysema_features_end first");
-  int rc = out ? multi_run(m, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout)
+  int rc = out ? multi_run(m, path, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout)
                : mfail(m, IFE_E_ARG, "null pointer");
   const size_t vox8 = rc == IFE_OK ? (size_t)(vol->nx * vol->ny * vol->nz) * IFE_NUM_FEATURES : 0;
   for (int s = 0; s < n_sigmas && rc == IFE_OK; ++s) rc = multi_fetch_scale(m, s, out + (size_t)s * vox8);
@@ -508,19 +554,12 @@ int ife_multi_emphysema_features(ife_multi *m, const void *image, int image_dtyp
   return rc != IFE_OK ? rc : drained;
 }
 
-// The scale loop of tools/ExtractFeatures.cxx:132-154 over several devices, one scale at a time
-// to the host: _begin uploads the slabs once, runs the prepass once and enqueues EVERY scale on
-// every device (nothing is waited for); _fetch(k) blocks until scale k of every slab has been
-// copied into `out` (the whole volume of that scale, host memory) while the later scales keep
-// computing; _end drains.  The inputs may be reused once _begin returns: it waits for the uploads
-// (from page-locked memory they run asynchronously to the host), not for the scales; `out` must
-// stay valid until its _fetch returns.
-int ife_multi_emphysema_features_begin(ife_multi *m, const void *image, int image_dtype, const void *mask,
-                                       int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
-                                       int n_sigmas, int layout) {
+// The _begin calls: every scale of `path` enqueued; returns once the uploads have landed.
+int multi_begin(ife_multi *m, MultiPath path, const void *image, int image_dtype, const void *mask,
+                int mask_dtype, const ife_volume_desc *vol, const float *sigmas, int n_sigmas, int layout) {
   if (!m) return IFE_E_ARG;
   if (m->streaming) return mfail(m, IFE_E_STATE, "a streaming call is already in flight");
-  int rc = multi_run(m, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout);
+  int rc = multi_run(m, path, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout);
   for (auto &R : m->ranks) {  // the caller may reuse image and mask from here on
     if (rc != IFE_OK) break;
     hipError_t e = hipSetDevice(R.dev);
@@ -533,6 +572,45 @@ int ife_multi_emphysema_features_begin(ife_multi *m, const void *image, int imag
   }
   m->streaming = true;
   return IFE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ife_multi_emphysema_features(ife_multi *m, const void *image, int image_dtype, const void *mask,
+                                 int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
+                                 int n_sigmas, float *out, int layout) {
+  return multi_features(m, MULTI_FD, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, out, layout);
+}
+
+// ife_differential_features over several devices: the same slabs and state chains, six Z jobs per
+// scale, and behind them only slab-local work (multi_run, MULTI_JET).
+int ife_multi_differential_features(ife_multi *m, const void *image, int image_dtype, const void *mask,
+                                    int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
+                                    int n_sigmas, float *out, int layout) {
+  return multi_features(m, MULTI_JET, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, out, layout);
+}
+
+// The scale loop of tools/ExtractFeatures.cxx:132-154 over several devices, one scale at a time
+// to the host: _begin uploads the slabs once, runs the prepass once and enqueues EVERY scale on
+// every device (nothing is waited for); _fetch(k) blocks until scale k of every slab has been
+// copied into `out` (the whole volume of that scale, host memory) while the later scales keep
+// computing; _end drains.  The inputs may be reused once _begin returns: it waits for the uploads
+// (from page-locked memory they run asynchronously to the host), not for the scales; `out` must
+// stay valid until its _fetch returns.
+int ife_multi_emphysema_features_begin(ife_multi *m, const void *image, int image_dtype, const void *mask,
+                                       int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
+                                       int n_sigmas, int layout) {
+  return multi_begin(m, MULTI_FD, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout);
+}
+
+// The same stream with every scale that of ife_multi_differential_features; _fetch and _end are
+// those of the stream above.
+int ife_multi_differential_features_begin(ife_multi *m, const void *image, int image_dtype, const void *mask,
+                                          int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
+                                          int n_sigmas, int layout) {
+  return multi_begin(m, MULTI_JET, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout);
 }
 
 int ife_multi_emphysema_features_fetch(ife_multi *m, int scale, float *out) {

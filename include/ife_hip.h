@@ -133,8 +133,9 @@ typedef enum {
    * workspace does).  A stream takes the value in force at its _begin; setting the option
    * between _begin and _fetch / _next changes nothing of what that stream delivers.
    * ife_emphysema_features, ife_differential_features, the jet and every ife_stage_* call name
-   * their arithmetic and ignore the option.  The differential path runs on one device:
-   * ife_multi_set_option refuses the value 1.  With 0 every call does exactly what it did
+   * their arithmetic and ignore the option.  The composite calls run the differential path on one
+   * device: ife_multi_set_option refuses the value 1 (ife_multi_differential_features names its
+   * arithmetic and runs on several).  With 0 every call does exactly what it did
    * before the option existed.  The library reads no environment variable for it (the host
    * Engine maps IFE_DIFFERENTIAL onto it). */
   IFE_OPT_DIFFERENTIAL = 13
@@ -425,6 +426,30 @@ int ife_stage_z_fused(ife_ctx *ctx, int direction, int njobs, const float *const
                       float *const *out, const ife_volume_desc *slab, int64_t line0, int64_t nlines,
                       const double *sigmas, int has_lo, int has_hi, const void *state_in,
                       void *state_out, void *const *ck);
+/* The three calls above with an order per job: orders[job] is 0 (ZeroOrder), 1 (FirstOrder) or 2
+ * (SecondOrder) as in ife_stage_recursive_gaussian_order; NULL means all zero, which is exactly
+ * the call above; any other value is IFE_E_ARG.  The recurrence has the same form for every
+ * order (four input taps, four feedback taps; only the coefficients differ), so state records,
+ * overlap planes and checkpoints are those of order 0, and the contract is the same: stitched
+ * over the slabs the result is bit for bit ife_stage_recursive_gaussian_order along z on the
+ * whole volume, for every order.
+ * ife_stage_z_sweep_order reads each plane ONCE for three consecutive jobs that have the same
+ * `in`, the same sigma and the orders 0, 1, 2 in that order (the three Z-level fields the
+ * differential path takes of one source): one lane then advances the three recursions side by
+ * side.  Every other job runs as in ife_stage_z_sweep.  Checkpoints, states and therefore every
+ * later result are the same bit for bit in either form; the job order only decides the form. */
+int ife_stage_z_sweep_order(ife_ctx *ctx, int direction, int njobs, const float *const *in,
+                            const ife_volume_desc *slab, int64_t line0, int64_t nlines,
+                            const double *sigmas, const int *orders, int has_neighbour,
+                            const void *state_in, void *state_out, void *const *ck);
+int ife_stage_z_combine_order(ife_ctx *ctx, int njobs, const float *const *in, float *const *out,
+                              const ife_volume_desc *slab, int64_t line0, int64_t nlines,
+                              const double *sigmas, const int *orders, int has_lo, int has_hi,
+                              void *const *ck);
+int ife_stage_z_fused_order(ife_ctx *ctx, int direction, int njobs, const float *const *in,
+                            float *const *out, const ife_volume_desc *slab, int64_t line0, int64_t nlines,
+                            const double *sigmas, const int *orders, int has_lo, int has_hi,
+                            const void *state_in, void *state_out, void *const *ck);
 /* The last axis pass of the normalized convolution in its quotient form
  * (NormalizedGaussianConvolutionImageFilter.hxx:51-61: the two smoothings and the Div functor):
  * job j filters num[j] and den[j] along `axis` (1 = y or 2 = z) with sigmas[j] and stores
@@ -443,6 +468,19 @@ int ife_stage_features(ife_ctx *ctx, const float *num, const float *den, const v
                        int mask_dtype, const ife_volume_desc *slab, int halo_lo, int halo_hi,
                        float *out, int layout);
 
+/* Everything of ife_differential_features behind the Z level, on a slab: zf[3*s + k] is the
+ * Z-level field of source s (0 = cT = float(image) * float(mask), 1 = c = float(mask), or the
+ * constant 1.0f without a mask) at order k, on the slab's own planes (what the ife_stage_z_*_order
+ * calls leave).  Runs the X level (12 fields), the Y level (20 fields) and the pointwise feature
+ * kernel in the context's trig mode: the code path and slot schedule of the one-device call behind
+ * its Z launch, so on one slab that is the whole volume the result is that call's bit for bit, and
+ * over several slabs too, since nothing behind the Z level crosses a plane.  Workspace: that of
+ * ife_differential_features on a volume of the slab's size, less its Z-level fields and sources.
+ * mask (NULL: all ones) and out cover the slab's planes; pointer alignment as in
+ * ife_differential_features (mask to its element size, interleaved out to 16 bytes); nx, ny >= 4. */
+int ife_stage_jet_features(ife_ctx *ctx, const float *const zf[6], const void *mask, int mask_dtype,
+                           const ife_volume_desc *slab, double sigma, float *out, int layout);
+
 /* ---- several devices in one process --------------------------------------------------
  *
  * The same Z-slab decomposition driven from C++ by ONE host thread: device r of the list
@@ -456,7 +494,9 @@ int ife_multi_create(const int *devices, int n_devices, ife_multi **out);
 void ife_multi_destroy(ife_multi *m);
 const char *ife_multi_last_error(const ife_multi *m);
 /* ife_ctx_set_option on every context of the engine.  IFE_OPT_DIFFERENTIAL 1 is IFE_E_ARG: the
- * differential path runs on one device (0 is accepted). */
+ * option selects the path of the COMPOSITE calls, and those run the differential path on one device
+ * (0 is accepted).  The call that names its arithmetic exists here as it does on one device:
+ * ife_multi_differential_features below. */
 int ife_multi_set_option(ife_multi *m, int option, int value);
 int ife_multi_emphysema_features(ife_multi *m, const void *image, int image_dtype,
                                  const void *mask, int mask_dtype, const ife_volume_desc *vol,
@@ -473,6 +513,20 @@ int ife_multi_emphysema_features_begin(ife_multi *m, const void *image, int imag
                                        const float *sigmas, int n_sigmas, int layout);
 int ife_multi_emphysema_features_fetch(ife_multi *m, int scale, float *out);
 int ife_multi_emphysema_features_end(ife_multi *m);
+/* ife_differential_features over the devices of the engine: same arguments, checks and errors as
+ * ife_multi_emphysema_features (every slab needs 4 planes: IFE_E_SIZE), host pointers in and out,
+ * blocks; the result equals ife_differential_features on one device bit for bit.  Every slab is
+ * uploaded with its overlap planes and cT and c are built over them; a scale is six Z jobs (cT and
+ * c at orders 0, 1, 2), carried through the two state chains like the two jobs of the
+ * finite-difference path; behind them every rank runs ife_stage_jet_features on its own planes.
+ * No plane is exchanged.  _begin is the streaming form; it shares
+ * ife_multi_emphysema_features_fetch / _end and their IFE_E_STATE rules. */
+int ife_multi_differential_features(ife_multi *m, const void *image, int image_dtype,
+                                    const void *mask, int mask_dtype, const ife_volume_desc *vol,
+                                    const float *sigmas, int n_sigmas, float *out, int layout);
+int ife_multi_differential_features_begin(ife_multi *m, const void *image, int image_dtype,
+                                          const void *mask, int mask_dtype, const ife_volume_desc *vol,
+                                          const float *sigmas, int n_sigmas, int layout);
 
 /* ---- rows f1 / f2: sample columns, equalizing histogram edges, dense histograms ------- *
  * The immediate consumer of the feature volume.  The samples never
