@@ -1,23 +1,23 @@
 // multi_capi.inc -- one process, several devices: the Z-slab decomposition of the feature
 // path (DESIGN.md section 6) driven from C++ with peer copies over xGMI.
 //
-// Same decomposition, kernels and schedule as image-feature-extraction_amd/slab.py (which
-// runs one process per GPU over RCCL): rank r of W owns a contiguous range of planes; the Z
-// recursion crosses slab boundaries as 32-byte state records (ife_stage_z_sweep for the
-// direction whose state reaches a rank first, ife_stage_z_fused for the other; every slab of the
-// raw data is uploaded with the neighbours' adjacent planes, IFE_Z_OVERLAP_LO below and _HI
-// above, so the input history of a state never travels), the last axis pass stores the quotient
-// (ife_stage_recursive_gaussian_quotient) and the stencil needs one boundary plane of that
-// smoothed value per scale from each neighbour.  Here one host thread enqueues everything: every "rank" is a
-// pair of ife_ctx (bulk stream, high-priority chain stream) on its device, transfers are
-// hipMemcpyPeerAsync on the sender's stream, and every dependency is a HIP event recorded
-// before it is waited for -- the chain items are enqueued in wavefront order (causal item i
-// at rank r in step r + i, anticausal in step W-1-r + i), so no wait can refer to an event
-// that has not been recorded.  The same device may appear more than once in the list (that
-// is how the tests exercise W > 1 on a one-GPU box); the reference has no counterpart
-// (SURVEY.md section 8e).  The differential path (ife_multi_differential_features) runs the same
-// slabs, uploads and state chains with six Z jobs per scale and nothing but slab-local work behind
-// them (multi_run, MultiPath).  Included by ife_capi.hip.
+// Same decomposition (slab_plan.hpp), kernels and schedule as image-feature-extraction_amd/slab.py,
+// which runs one process per GPU over RCCL: the Z recursion crosses slab boundaries as 32-byte
+// state records (ife_stage_z_sweep for the direction whose state reaches a rank first,
+// ife_stage_z_fused for the other; the raw data carries its overlap planes, so the input history
+// of a state never travels), the last axis pass stores the quotient and the stencil needs one
+// boundary plane of that smoothed value per scale from each neighbour.  Here one host thread
+// enqueues everything: every "rank" is a pair of ife_ctx (bulk stream, high-priority chain stream)
+// on its device, transfers are hipMemcpyPeerAsync on the sender's stream, and every dependency is
+// a HIP event recorded before it is waited for (for_each_chain_step says why the chains can).  The
+// same device may appear more than once in the list (that is how the tests exercise W > 1 on a
+// one-GPU box); the reference has no counterpart (SURVEY.md section 8e).
+//
+// A call (MultiCall) is the phases of multi_run: multi_check (arguments), multi_plan (slabs, items,
+// groups), multi_reserve (every buffer), multi_upload, multi_prepare (prepass), multi_chains
+// (multi_sweep per chain step), then multi_bulk_fd or multi_bulk_jet (MultiPath: the differential
+// path differs in the Z jobs of a scale and in the bulk phase).  Included by ife_capi.hip.
+#include "slab_plan.hpp"
 
 namespace {
 
@@ -25,13 +25,18 @@ struct MultiRank {
   int dev = 0;
   ife_ctx *bulk = nullptr, *chain = nullptr;
   hipStream_t sb = nullptr, sc = nullptr, sd = nullptr;  // bulk, boundary chain, downloads
-  int64_t z0 = 0, nzl = 0;
-  int64_t lo = 0, hi = 0;  // planes of the neighbours carried below / above the slab's own
+  SlabRank cut;          // the slab of the call in flight: z0, nzl and the overlap lo, hi
+  int jps = 1, nf = 1;   // its Z jobs and its fields per scale
   DevBuf img, mask, src[2], out;
-  std::vector<DevBuf> zo, xo, pad, ck;        // [scale * nf + field]
-  std::vector<DevBuf> c_in, c_out, a_in, a_out;  // [item]
-  std::vector<hipEvent_t> ev;                  // every event of a run, destroyed at its end
-  hipEvent_t uploaded = nullptr;               // behind the run's uploads from host memory (one of ev)
+  std::vector<DevBuf> zo, ck, xo, pad;           // [scale * jps + job] (zo, ck), [scale * nf + field], [scale]
+  std::vector<DevBuf> c_in, c_out, a_in, a_out;  // [item]: causal / anticausal state, incoming / outgoing
+  std::vector<hipEvent_t> ev;                    // every event of a run, destroyed at its end
+  hipEvent_t uploaded = nullptr;                 // behind the run's uploads from host memory (one of ev)
+  DevBuf &z_out(int s, int k) { return zo[(size_t)(s * jps + k)]; }  // Z output / checkpoints of job k of scale s
+  DevBuf &z_ck(int s, int k) { return ck[(size_t)(s * jps + k)]; }
+  DevBuf &x_out(int s, int f) { return xo[(size_t)(s * nf + f)]; }   // X output of field f of scale s
+  DevBuf &state_in(int d, int i) { return (d == 0 ? c_in : a_in)[(size_t)i]; }
+  DevBuf &state_out(int d, int i) { return (d == 0 ? c_out : a_out)[(size_t)i]; }
 };
 
 }  // namespace
@@ -39,7 +44,6 @@ struct MultiRank {
 struct ife_multi {
   std::vector<MultiRank> ranks;
   std::string err;
-  int trig_mode = -1;  // -1: the library default
   // streaming form (ife_multi_emphysema_features_begin / _fetch / _end): the geometry of the
   // call in flight and, per rank and scale, the event behind that scale's feature launch
   bool streaming = false;
@@ -199,9 +203,7 @@ int ife_multi_set_option(ife_multi *m, int option, int value) {
 
 namespace {
 
-// The feature path of a run.  Both cut the volume into the same slabs, upload them with the same
-// overlap and carry the Z recursion through the same two state chains; they differ in the Z jobs
-// of a scale and in what the bulk stream makes of the Z output:
+// The feature path of a call: the Z jobs of a scale and what the bulk stream makes of the Z output.
 //   MULTI_FD   numerator and denominator (or the image alone), order 0; then X, Y with the
 //              quotient, one stencil plane from each neighbour, ife_stage_features;
 //   MULTI_JET  cT and c at orders 0, 1, 2, source-major (so that the lean sweeps read every plane
@@ -209,312 +211,322 @@ namespace {
 //              plane is exchanged.  c is the constant 1.0f without a mask, as jet_sources makes it.
 enum MultiPath { MULTI_FD, MULTI_JET };
 
-// Everything a feature call enqueues; may return early with work in flight and events alive --
-// the caller drains (multi_drain) whatever this returns.
-int multi_run(ife_multi *m, MultiPath path, const void *image, int image_dtype, const void *mask, int mask_dtype,
-              const ife_volume_desc *vol, const float *sigmas, int n_sigmas, int layout) {
-  if (!vol || !image || !sigmas) return mfail(m, IFE_E_ARG, "null pointer");
+// One feature call: its arguments, its plan (slab_plan.hpp) and the events of its state chains.
+struct MultiCall {
+  ife_multi *m;
+  MultiPath path;
+  const void *image; int image_dtype;
+  const void *mask; int mask_dtype;
+  const ife_volume_desc *vol;
+  const float *sigmas; int n_sigmas, layout;
+  SlabPlan plan = {};
+  // [direction][rank][item].  arrived: the incoming state has landed in the rank's buffer;
+  // swept: the sweep has run (its checkpoints or its Z output are in place)
+  std::vector<std::vector<std::vector<hipEvent_t>>> arrived = {}, swept = {};
+
+  MultiRank &rank(int r) const { return m->ranks[(size_t)r]; }
+  bool jet() const { return path == MULTI_JET; }
+  int nf() const { return mask ? 2 : 1; }
+  int nsrc() const { return jet() ? 2 : nf(); }  // float sources of the Z jobs
+  int jps() const { return jet() ? 6 : nf(); }   // Z jobs per scale: source-major, jps / nsrc orders each
+  size_t isz() const { return dtype_size(image_dtype); }
+  size_t msz() const { return mask ? dtype_size(mask_dtype) : 0; }
+  double sigma(int s) const { return (double)sigmas[s]; }
+  ife_volume_desc slab(int64_t planes) const { return {vol->nx, vol->ny, planes, vol->sx, vol->sy, vol->sz}; }
+  const void *own_mask(const MultiRank &R) const {  // of the slab's own planes
+    return mask ? (const char *)R.mask.p + (size_t)(R.cut.lo * plan.plane) * msz() : nullptr;
+  }
+  float *out(const MultiRank &R, int s) const {  // scale s of the slab's features
+    return (float *)R.out.p + (size_t)s * (size_t)(R.cut.nzl * plan.plane) * IFE_NUM_FEATURES;
+  }
+};
+
+int multi_check(const MultiCall &c) {
+  ife_multi *m = c.m;
+  if (!c.vol || !c.image || !c.sigmas) return mfail(m, IFE_E_ARG, "null pointer");
   const int W = (int)m->ranks.size();
-  const int64_t nx = vol->nx, ny = vol->ny, nz = vol->nz;
-  // the shared checks report through the first rank's context
-  ife_ctx *c0 = m->ranks[0].bulk;
+  const int64_t nx = c.vol->nx, ny = c.vol->ny, nz = c.vol->nz;
+  ife_ctx *c0 = c.rank(0).bulk;  // the shared checks report through the first rank's context
   int rc;
-  if ((rc = check_sigmas(c0, sigmas, n_sigmas)) || (rc = check_image_dtype(c0, image_dtype)) ||
-      (rc = check_mask_dtype(c0, mask, mask_dtype, true)) || (rc = check_layout_mem(c0, layout, IFE_MEM_HOST)))
+  if ((rc = check_sigmas(c0, c.sigmas, c.n_sigmas)) || (rc = check_image_dtype(c0, c.image_dtype)) ||
+      (rc = check_mask_dtype(c0, c.mask, c.mask_dtype, true)) || (rc = check_layout_mem(c0, c.layout, IFE_MEM_HOST)))
     return mfail(m, rc, "%s", c0->err.c_str());
   if (nx < 4 || ny < 4 || nz < (int64_t)4 * W)
     return mfail(m, IFE_E_SIZE, "every Z-slab needs at least 4 planes and every axis 4 voxels "
                                 "(%lld x %lld x %lld over %d devices)",
                  (long long)nx, (long long)ny, (long long)nz, W);
-  if ((rc = check_vol(c0, vol, false))) return mfail(m, rc, "%s", c0->err.c_str());  // spacing
-  const bool jet = path == MULTI_JET;
-  const int nf = mask ? 2 : 1, S = n_sigmas;
-  const int nsrc = jet ? 2 : nf;  // float sources of the Z jobs
-  const int jps = jet ? 6 : nf;   // Z jobs per scale: job s * jps + k * (jps / nsrc) + order
-  const int64_t plane = nx * ny;
-  const size_t isz = dtype_size(image_dtype), msz = mask ? dtype_size(mask_dtype) : 0;
-  // slabs: nz / W planes each, the remainder spread over the first ranks
-  {
-    int64_t z = 0;
-    for (int r = 0; r < W; ++r) {
-      m->ranks[(size_t)r].z0 = z;
-      m->ranks[(size_t)r].nzl = nz / W + (r < nz % W ? 1 : 0);
-      m->ranks[(size_t)r].lo = r > 0 ? IFE_Z_OVERLAP_LO : 0;
-      m->ranks[(size_t)r].hi = r < W - 1 ? IFE_Z_OVERLAP_HI : 0;
-      z += m->ranks[(size_t)r].nzl;
-    }
-  }
-  // chain items: (scale group, line group); groups as slab.py chooses them
-  const int max_jobs = IIR_MAX_JOBS / jps;  // scales per chain item (one on the differential path)
-  const int spi = std::max(1, std::min(max_jobs, S));
-  std::vector<std::vector<int>> sgroups;
-  for (int s0 = 0; s0 < S; s0 += spi) {
-    sgroups.emplace_back();
-    for (int s = s0; s < std::min(S, s0 + spi); ++s) sgroups.back().push_back(s);
-  }
-  int G = W == 1 ? 1 : 4;
-  G = (int)std::max<int64_t>(1, std::min<int64_t>(G, (plane + 255) / 256));
-  const int64_t per = ((plane + G - 1) / G + 255) / 256 * 256;
-  std::vector<std::pair<int64_t, int64_t>> lgroups;
-  for (int64_t l0 = 0; l0 < plane; l0 += per) lgroups.emplace_back(l0, std::min(plane, l0 + per) - l0);
-  struct Item { int q, g; };
-  std::vector<Item> items;
-  for (int q = 0; q < (int)sgroups.size(); ++q)
-    for (int g = 0; g < (int)lgroups.size(); ++g) items.push_back(Item{q, g});
-  const int NI = (int)items.size();
-  // bulk groups: the first scale group alone, the rest merged up to max_jobs jobs per launch
-  std::vector<std::vector<int>> bgroups(1, std::vector<int>(1, 0));
-  for (int q = 1; q < (int)sgroups.size(); ++q) {
-    size_t n_sc = sgroups[(size_t)q].size();
-    for (int k : bgroups.back()) n_sc += sgroups[(size_t)k].size();
-    if (bgroups.size() > 1 && (int)n_sc <= max_jobs) bgroups.back().push_back(q);
-    else bgroups.emplace_back(1, q);
-  }
+  if ((rc = check_vol(c0, c.vol, false))) return mfail(m, rc, "%s", c0->err.c_str());  // spacing
+  return IFE_OK;
+}
 
+// The plan of the call, and its geometry on every rank and (for the streaming form) on the engine.
+void multi_plan(MultiCall &c) {
+  ife_multi *m = c.m;
+  const int W = (int)m->ranks.size(), S = c.n_sigmas;
+  c.plan = slab_plan(c.vol->nx, c.vol->ny, c.vol->nz, W, S, c.jps(), IIR_MAX_JOBS);
+  for (int r = 0; r < W; ++r) c.rank(r).cut = c.plan.rank(r), c.rank(r).jps = c.jps(), c.rank(r).nf = c.nf();
+  c.arrived.assign(2, std::vector<std::vector<hipEvent_t>>(W, std::vector<hipEvent_t>(c.plan.n_items(), nullptr)));
+  c.swept = c.arrived;
+  m->s_done.assign(W, std::vector<hipEvent_t>(S, nullptr));
+  m->s_vol = *c.vol, m->s_scales = S, m->s_layout = c.layout;
   if (getenv("IFE_MULTI_TRACE"))  // one line per upload + prepass: the host-tool tests count them
     fprintf(stderr, "ife_multi: upload and prepass of %lld x %lld x %lld over %d devices, %d scales\n",
-            (long long)nx, (long long)ny, (long long)nz, W, S);
-  // ---- buffers, inputs ------------------------------------------------------------------
-  for (int r = 0; r < W; ++r) {
-    MultiRank &R = m->ranks[(size_t)r];
-    const size_t nvl = (size_t)(R.nzl * plane);
-    const size_t nve = (size_t)((R.lo + R.nzl + R.hi) * plane);  // with the neighbours' planes
-    ife_volume_desc slab = {nx, ny, R.nzl, vol->sx, vol->sy, vol->sz};
-    int rc = mensure(m, R, R.img, nve * isz);
-    if (!rc && mask) rc = mensure(m, R, R.mask, nve * msz);
-    for (int k = 0; k < nsrc && !rc; ++k) rc = mensure(m, R, R.src[k], (nve + 3) / 4 * 16);  // whole 16-byte pieces
-    if (!rc) rc = mensure(m, R, R.out, nvl * IFE_NUM_FEATURES * 4 * (size_t)S);
-    // (never shrunk: an engine that runs both paths in turn keeps the buffers of both)
-    R.zo.resize(std::max(R.zo.size(), (size_t)(S * jps))); R.xo.resize(std::max(R.xo.size(), (size_t)(S * nf)));
-    R.pad.resize(std::max(R.pad.size(), (size_t)S)); R.ck.resize(std::max(R.ck.size(), (size_t)(S * jps)));
-    for (int j = 0; j < S * jps && !rc; ++j) {
-      rc = mensure(m, R, R.zo[(size_t)j], nvl * 4);
-      if (!rc) rc = mensure(m, R, R.ck[(size_t)j], ife_stage_z_ck_bytes(&slab));
-    }
-    for (int j = 0; j < S * nf && !rc && !jet; ++j) rc = mensure(m, R, R.xo[(size_t)j], nvl * 4);
-    for (int j = 0; j < S && !rc && !jet; ++j)  // the smoothed value of a scale with one halo plane each side
-      rc = mensure(m, R, R.pad[(size_t)j], (size_t)((R.nzl + 2) * plane) * 4);
-    const size_t ni = std::max(R.c_in.size(), (size_t)NI);
-    R.c_in.resize(ni); R.c_out.resize(ni); R.a_in.resize(ni); R.a_out.resize(ni);
-    for (int i = 0; i < NI && !rc; ++i) {
-      const size_t sb = sgroups[(size_t)items[(size_t)i].q].size() * (size_t)jps * IFE_Z_STATE_BYTES *
-                        (size_t)lgroups[(size_t)items[(size_t)i].g].second;
-      rc = mensure(m, R, R.c_in[(size_t)i], sb);
-      if (!rc) rc = mensure(m, R, R.c_out[(size_t)i], sb);
-      if (!rc) rc = mensure(m, R, R.a_in[(size_t)i], sb);
-      if (!rc) rc = mensure(m, R, R.a_out[(size_t)i], sb);
-    }
-    if (rc) return rc;
-    IFE_MHIP(m, hipSetDevice(R.dev));
-    IFE_MHIP(m, hipMemcpyAsync(R.img.p, (const char *)image + (size_t)((R.z0 - R.lo) * plane) * isz, nve * isz,
-                               hipMemcpyHostToDevice, R.sb));
-    if (mask)
-      IFE_MHIP(m, hipMemcpyAsync(R.mask.p, (const char *)mask + (size_t)((R.z0 - R.lo) * plane) * msz, nve * msz,
-                                 hipMemcpyHostToDevice, R.sb));
-    if ((rc = mrecord(m, R, R.sb, &R.uploaded))) return rc;
-  }
+            (long long)c.vol->nx, (long long)c.vol->ny, (long long)c.vol->nz, W, S);
+}
 
-  // ---- prepare, then the two state chains in wavefront order -----------------------------
-  std::vector<hipEvent_t> prepared((size_t)W, nullptr);
-  for (int r = 0; r < W; ++r) {
-    MultiRank &R = m->ranks[(size_t)r];
-    ife_volume_desc ext = {nx, ny, R.lo + R.nzl + R.hi, vol->sx, vol->sy, vol->sz};  // the prepass covers the overlap
-    IFE_MCTX(m, R, R.bulk, ife_stage_prepare(R.bulk, R.img.p, image_dtype, mask ? R.mask.p : nullptr, mask_dtype,
-                                             &ext, 1, (float *)R.src[0].p, mask ? (float *)R.src[1].p : nullptr));
-    if (jet && !mask) {  // certainty one everywhere: the second source is the constant
-      const int64_t n4 = ((R.lo + R.nzl + R.hi) * plane + 3) / 4;
+// Every buffer of the call on every rank; never shrunk, so one engine keeps the buffers of both paths.
+int multi_reserve(MultiCall &c) {
+  const SlabPlan &p = c.plan;
+  const int S = p.S, NI = p.n_items();
+  for (int r = 0; r < p.W; ++r) {
+    MultiRank &R = c.rank(r);
+    const size_t nvl = p.voxels(r), nve = p.voxels_ext(r);  // own planes; with the neighbours' planes
+    const ife_volume_desc slab = c.slab(R.cut.nzl);
+    int rc = IFE_OK;
+    auto need = [&](DevBuf &b, size_t bytes) { rc = rc ? rc : mensure(c.m, R, b, bytes); };
+    auto at_least = [](std::vector<DevBuf> &v, int n) { v.resize(std::max(v.size(), (size_t)n)); };
+    need(R.img, nve * c.isz());
+    if (c.mask) need(R.mask, nve * c.msz());
+    for (int k = 0; k < c.nsrc(); ++k) need(R.src[k], (nve + 3) / 4 * 16);  // whole 16-byte pieces
+    need(R.out, nvl * IFE_NUM_FEATURES * 4 * S);
+    at_least(R.zo, S * R.jps), at_least(R.ck, S * R.jps), at_least(R.xo, S * R.nf), at_least(R.pad, S);
+    for (int s = 0; s < S; ++s)
+      for (int k = 0; k < R.jps; ++k) need(R.z_out(s, k), nvl * 4), need(R.z_ck(s, k), ife_stage_z_ck_bytes(&slab));
+    for (int s = 0; s < S && !c.jet(); ++s)
+      for (int f = 0; f < R.nf; ++f) need(R.x_out(s, f), nvl * 4);
+    for (int s = 0; s < S && !c.jet(); ++s)  // the smoothed value of a scale with one halo plane each side
+      need(R.pad[s], (nvl + 2 * p.plane) * 4);
+    at_least(R.c_in, NI), at_least(R.c_out, NI), at_least(R.a_in, NI), at_least(R.a_out, NI);
+    for (int i = 0; i < NI; ++i)
+      for (int d = 0; d < 2; ++d) need(R.state_in(d, i), p.state_bytes(i)), need(R.state_out(d, i), p.state_bytes(i));
+    if (rc) return rc;
+  }
+  return IFE_OK;
+}
+
+// Every slab of the raw data with its overlap, host to device on the bulk streams.
+int multi_upload(MultiCall &c) {
+  for (int r = 0; r < c.plan.W; ++r) {
+    MultiRank &R = c.rank(r);
+    const size_t first = c.plan.first_voxel_ext(r), nve = c.plan.voxels_ext(r);
+    IFE_MHIP(c.m, hipSetDevice(R.dev));
+    IFE_MHIP(c.m, hipMemcpyAsync(R.img.p, (const char *)c.image + first * c.isz(), nve * c.isz(),
+                                 hipMemcpyHostToDevice, R.sb));
+    if (c.mask)
+      IFE_MHIP(c.m, hipMemcpyAsync(R.mask.p, (const char *)c.mask + first * c.msz(), nve * c.msz(),
+                                   hipMemcpyHostToDevice, R.sb));
+    if (int rc = mrecord(c.m, R, R.sb, &R.uploaded)) return rc;
+  }
+  return IFE_OK;
+}
+
+// The prepass over every slab and its overlap (bulk stream); the chain stream waits for it.
+int multi_prepare(MultiCall &c) {
+  ife_multi *m = c.m;
+  for (int r = 0; r < c.plan.W; ++r) {
+    MultiRank &R = c.rank(r);
+    const ife_volume_desc ext = c.slab(c.plan.planes_ext(r));
+    IFE_MCTX(m, R, R.bulk, ife_stage_prepare(R.bulk, R.img.p, c.image_dtype, c.mask ? R.mask.p : nullptr, c.mask_dtype,
+                                             &ext, 1, (float *)R.src[0].p, c.mask ? (float *)R.src[1].p : nullptr));
+    if (c.jet() && !c.mask) {  // certainty one everywhere: the second source is the constant
+      const int64_t n4 = (c.plan.voxels_ext(r) + 3) / 4;
       const unsigned blocks = (unsigned)std::min<int64_t>((n4 + 255) / 256, 0x7fffffff);
       IFE_MHIP(m, hipSetDevice(R.dev));
       hipLaunchKernelGGL(stream_fill_kernel, dim3(blocks), dim3(256), 0, R.sb, (float4 *)R.src[1].p, n4, 1.0f);
       IFE_MHIP(m, hipGetLastError());
     }
-    int rc = mrecord(m, R, R.sb, &prepared[(size_t)r]);
-    if (!rc) rc = mwait(m, R, R.sc, prepared[(size_t)r]);
-    if (rc) return rc;
-  }
-  // arrived[d][r][i]: the incoming state of item i, direction d, has landed in rank r's buffer
-  std::vector<std::vector<std::vector<hipEvent_t>>> arrived(
-      2, std::vector<std::vector<hipEvent_t>>((size_t)W, std::vector<hipEvent_t>((size_t)NI, nullptr)));
-  auto swept = arrived;  // swept[d][r][i]: the sweep has run (checkpoints are in place)
-  for (int t = 0; t < NI + W - 1; ++t) {
-    for (int r = 0; r < W; ++r) {
-      MultiRank &R = m->ranks[(size_t)r];
-      ife_volume_desc slab = {nx, ny, R.nzl, vol->sx, vol->sy, vol->sz};
-      for (int d = 0; d < 2; ++d) {
-        const int i = d == 0 ? t - r : t - (W - 1 - r);
-        if (i < 0 || i >= NI) continue;
-        const std::vector<int> &ss = sgroups[(size_t)items[(size_t)i].q];
-        const int64_t l0 = lgroups[(size_t)items[(size_t)i].g].first, nl = lgroups[(size_t)items[(size_t)i].g].second;
-        const bool has_nb = d == 0 ? r > 0 : r < W - 1;
-        const float *in[IIR_MAX_JOBS];
-        float *zo_w[IIR_MAX_JOBS];
-        void *ck[IIR_MAX_JOBS];
-        double sg[IIR_MAX_JOBS];
-        int ord[IIR_MAX_JOBS];
-        int nj = 0;
-        for (int s : ss)
-          for (int k = 0; k < jps; ++k, ++nj) {
-            in[nj] = (const float *)R.src[k / (jps / nsrc)].p + R.lo * plane;  // the slab's own plane 0
-            zo_w[nj] = (float *)R.zo[(size_t)(s * jps + k)].p;
-            ck[nj] = R.ck[(size_t)(s * jps + k)].p;
-            sg[nj] = (double)sigmas[s];
-            ord[nj] = k % (jps / nsrc);
-          }
-        const int *orders = jet ? ord : nullptr;
-        int rc = has_nb ? mwait(m, R, R.sc, arrived[(size_t)d][(size_t)r][(size_t)i]) : IFE_OK;
-        if (rc) return rc;
-        DevBuf &sin = d == 0 ? R.c_in[(size_t)i] : R.a_in[(size_t)i];
-        DevBuf &sout = d == 0 ? R.c_out[(size_t)i] : R.a_out[(size_t)i];
-        // the direction whose state reaches this rank first is a lean sweep, the other one is
-        // carried through the slab together with the combine (slab.py, SlabEngine.lean)
-        const int lean = r <= W - 1 - r ? 0 : 1;
-        if (d == lean) {
-          IFE_MCTX(m, R, R.chain, ife_stage_z_sweep_order(R.chain, d, nj, in, &slab, l0, nl, sg, orders, has_nb ? 1 : 0,
-                                                          has_nb ? sin.p : nullptr, sout.p, ck));
-        } else {
-          IFE_MCTX(m, R, R.chain, ife_stage_z_fused_order(R.chain, d, nj, in, zo_w, &slab, l0, nl, sg, orders, r > 0,
-                                                          r < W - 1, has_nb ? sin.p : nullptr, sout.p, ck));
-        }
-        if ((rc = mrecord(m, R, R.sc, &swept[(size_t)d][(size_t)r][(size_t)i]))) return rc;
-        const int nb = d == 0 ? r + 1 : r - 1;
-        if (nb >= 0 && nb < W) {
-          MultiRank &N = m->ranks[(size_t)nb];
-          DevBuf &dst = d == 0 ? N.c_in[(size_t)i] : N.a_in[(size_t)i];
-          if ((rc = mcopy(m, R, R.sc, N, dst.p, sout.p, (size_t)nj * IFE_Z_STATE_BYTES * (size_t)nl))) return rc;
-          if ((rc = mrecord(m, R, R.sc, &arrived[(size_t)d][(size_t)nb][(size_t)i]))) return rc;
-        }
-      }
-    }
-  }
-
-  // ---- bulk: X, Y (quotient), stencil planes, features, per bulk group ------------------------
-  const size_t pb = (size_t)plane * 4;
-  m->s_done.assign((size_t)W, std::vector<hipEvent_t>((size_t)S, nullptr));
-  m->s_vol = *vol;
-  m->s_scales = S;
-  m->s_layout = layout;
-  if (jet) {
-    // ---- bulk of the differential path: per scale X level, Y level and the pointwise pass, all
-    // slab-local (a chain item holds one scale: scale group q is scale q) ----------------------
-    for (int s = 0; s < S; ++s)
-      for (int r = 0; r < W; ++r) {
-        MultiRank &R = m->ranks[(size_t)r];
-        ife_volume_desc slab = {nx, ny, R.nzl, vol->sx, vol->sy, vol->sz};
-        const int fat = r <= W - 1 - r ? 1 : 0;
-        for (int i = 0; i < NI; ++i)
-          if (items[(size_t)i].q == s) {
-            int rc = mwait(m, R, R.sb, swept[(size_t)fat][(size_t)r][(size_t)i]);  // the fused kernels wrote the Z output
-            if (rc) return rc;
-          }
-        const float *zf[6];
-        for (int k = 0; k < 6; ++k) zf[k] = (const float *)R.zo[(size_t)(s * 6 + k)].p;
-        const void *own_mask = mask ? (const char *)R.mask.p + (size_t)(R.lo * plane) * msz : nullptr;
-        const size_t scale_out = (size_t)(R.nzl * plane) * IFE_NUM_FEATURES;
-        IFE_MCTX(m, R, R.bulk, ife_stage_jet_features(R.bulk, zf, own_mask, mask_dtype, &slab, (double)sigmas[s],
-                                                      (float *)R.out.p + (size_t)s * scale_out, layout));
-        int rc = mrecord(m, R, R.sb, &m->s_done[(size_t)r][(size_t)s]);
-        if (rc) return rc;
-      }
-    return IFE_OK;
-  }
-  for (const std::vector<int> &qs : bgroups) {
-    std::vector<int> ss;
-    for (int q : qs) for (int s : sgroups[(size_t)q]) ss.push_back(s);
-    const int nj = (int)ss.size() * nf, ns = (int)ss.size();
-    for (int r = 0; r < W; ++r) {
-      MultiRank &R = m->ranks[(size_t)r];
-      ife_volume_desc slab = {nx, ny, R.nzl, vol->sx, vol->sy, vol->sz};
-      const int fat = r <= W - 1 - r ? 1 : 0;
-      for (int i = 0; i < NI; ++i)
-        if (std::find(qs.begin(), qs.end(), items[(size_t)i].q) != qs.end()) {
-          int rc = mwait(m, R, R.sb, swept[(size_t)fat][(size_t)r][(size_t)i]);  // the fused kernels wrote the Z output
-          if (rc) return rc;
-        }
-      const float *zo[IIR_MAX_JOBS], *xnum[IIR_MAX_JOBS], *xden[IIR_MAX_JOBS];
-      float *xo_w[IIR_MAX_JOBS], *pad1[IIR_MAX_JOBS];
-      double sg[IIR_MAX_JOBS], sg1[IIR_MAX_JOBS];
-      int j = 0, js = 0;
-      for (int s : ss) {
-        for (int k = 0; k < nf; ++k, ++j) {
-          const size_t b = (size_t)(s * nf + k);
-          zo[j] = (const float *)R.zo[b].p;
-          xo_w[j] = (float *)R.xo[b].p;
-          sg[j] = (double)sigmas[s];
-        }
-        xnum[js] = (const float *)R.xo[(size_t)(s * nf)].p;
-        xden[js] = nf == 2 ? (const float *)R.xo[(size_t)(s * nf + 1)].p : nullptr;
-        pad1[js] = (float *)R.pad[(size_t)s].p + plane;  // planes 1 .. nzl of [nzl + 2]
-        sg1[js] = (double)sigmas[s];
-        ++js;
-      }
-      IFE_MCTX(m, R, R.bulk, ife_stage_recursive_gaussian_batch(R.bulk, nj, zo, xo_w, &slab, 0, sg, 1));
-      if (nf == 2)
-        IFE_MCTX(m, R, R.bulk, ife_stage_recursive_gaussian_quotient(R.bulk, ns, xnum, xden, pad1, &slab, 1, sg1));
-      else
-        IFE_MCTX(m, R, R.bulk, ife_stage_recursive_gaussian_batch(R.bulk, ns, xnum, pad1, &slab, 1, sg1, 1));
-    }
-    // boundary planes of the smoothed value to the neighbours (on the sender's bulk stream,
-    // behind its Y pass)
-    std::vector<hipEvent_t> from_lo((size_t)W, nullptr), from_hi((size_t)W, nullptr);
-    for (int r = 0; r < W; ++r) {
-      MultiRank &R = m->ranks[(size_t)r];
-      for (int side = 0; side < 2; ++side) {
-        const int nb = side == 0 ? r - 1 : r + 1;
-        if (nb < 0 || nb >= W) continue;
-        MultiRank &N = m->ranks[(size_t)nb];
-        for (int s : ss) {
-          const char *mine = (const char *)R.pad[(size_t)s].p + (side == 0 ? pb : (size_t)R.nzl * pb);  // first / last plane
-          char *theirs = (char *)N.pad[(size_t)s].p + (side == 0 ? (size_t)(N.nzl + 1) * pb : 0);        // its hi / lo halo
-          int rc = mcopy(m, R, R.sb, N, theirs, mine, pb);
-          if (rc) return rc;
-        }
-        int rc = mrecord(m, R, R.sb, side == 0 ? &from_hi[(size_t)nb] : &from_lo[(size_t)nb]);
-        if (rc) return rc;
-      }
-    }
-    for (int r = 0; r < W; ++r) {
-      MultiRank &R = m->ranks[(size_t)r];
-      ife_volume_desc slab = {nx, ny, R.nzl, vol->sx, vol->sy, vol->sz};
-      int rc = mwait(m, R, R.sb, from_lo[(size_t)r]);
-      if (!rc) rc = mwait(m, R, R.sb, from_hi[(size_t)r]);
-      if (rc) return rc;
-      const int lo = r > 0 ? 1 : 0, hi = r < W - 1 ? 1 : 0;
-      const size_t first = lo ? 0 : (size_t)plane;  // without a lower neighbour the buffer starts at plane 1
-      const size_t scale_out = (size_t)(R.nzl * plane) * IFE_NUM_FEATURES;
-      for (int s : ss) {
-        const float *val = (const float *)R.pad[(size_t)s].p + first;
-        const void *own_mask = mask ? (const char *)R.mask.p + (size_t)(R.lo * plane) * msz : nullptr;
-        IFE_MCTX(m, R, R.bulk, ife_stage_features(R.bulk, val, nullptr, own_mask, mask_dtype, &slab, lo,
-                                                  hi, (float *)R.out.p + (size_t)s * scale_out, layout));
-        if ((rc = mrecord(m, R, R.sb, &m->s_done[(size_t)r][(size_t)s]))) return rc;
-      }
-    }
+    hipEvent_t prepared = nullptr;
+    if (int rc = mrecord(m, R, R.sb, &prepared)) return rc;
+    if (int rc = mwait(m, R, R.sc, prepared)) return rc;
   }
   return IFE_OK;
+}
+
+// The job tables of a Z launch at rank R over the scales ss (those of a chain item).  Job k of a
+// scale reads source k / (jps / nsrc) at order k % (jps / nsrc), from the slab's own plane 0 on.
+struct ZJobs {
+  const float *in[IIR_MAX_JOBS]; float *zo[IIR_MAX_JOBS]; void *ck[IIR_MAX_JOBS];
+  double sigma[IIR_MAX_JOBS]; int order[IIR_MAX_JOBS], n = 0;
+};
+ZJobs z_jobs(const MultiCall &c, MultiRank &R, const std::vector<int> &ss) {
+  ZJobs j;
+  const int orders = c.jps() / c.nsrc();
+  for (int s : ss)
+    for (int k = 0; k < c.jps(); ++k, ++j.n) {
+      j.in[j.n] = (const float *)R.src[k / orders].p + R.cut.lo * c.plan.plane;
+      j.zo[j.n] = (float *)R.z_out(s, k).p;
+      j.ck[j.n] = R.z_ck(s, k).p;
+      j.sigma[j.n] = c.sigma(s);
+      j.order[j.n] = k % orders;
+    }
+  return j;
+}
+
+// One step of a state chain (chain stream): wait for the state, sweep, hand the state on.
+int multi_sweep(MultiCall &c, int r, int d, int i) {
+  ife_multi *m = c.m;
+  const SlabPlan &p = c.plan;
+  MultiRank &R = c.rank(r);
+  const ife_volume_desc slab = c.slab(R.cut.nzl);
+  const SlabLines &ln = p.lines(i);
+  const bool has_nb = p.has_neighbour(r, d);
+  const ZJobs j = z_jobs(c, R, p.scales(i));
+  const int *orders = c.jet() ? j.order : nullptr;
+  int rc = has_nb ? mwait(m, R, R.sc, c.arrived[d][r][i]) : IFE_OK;
+  if (rc) return rc;
+  const void *sin = has_nb ? R.state_in(d, i).p : nullptr;
+  void *sout = R.state_out(d, i).p;
+  if (d == p.lean(r))
+    IFE_MCTX(m, R, R.chain, ife_stage_z_sweep_order(R.chain, d, j.n, j.in, &slab, ln.line0, ln.nlines, j.sigma, orders,
+                                                    has_nb ? 1 : 0, sin, sout, j.ck));
+  else
+    IFE_MCTX(m, R, R.chain, ife_stage_z_fused_order(R.chain, d, j.n, j.in, j.zo, &slab, ln.line0, ln.nlines, j.sigma,
+                                                    orders, r > 0, r < p.W - 1, sin, sout, j.ck));
+  if ((rc = mrecord(m, R, R.sc, &c.swept[d][r][i]))) return rc;
+  const int nb = p.next(r, d);
+  if (nb >= 0 && nb < p.W) {
+    MultiRank &N = c.rank(nb);
+    if ((rc = mcopy(m, R, R.sc, N, N.state_in(d, i).p, sout, p.state_bytes(i)))) return rc;
+    if ((rc = mrecord(m, R, R.sc, &c.arrived[d][nb][i]))) return rc;
+  }
+  return IFE_OK;
+}
+
+// The two state chains, in the order of for_each_chain_step (slab_plan.hpp).
+int multi_chains(MultiCall &c) {
+  return for_each_chain_step(c.plan, [&](int, int r, int d, int i) { return multi_sweep(c, r, d, i); });
+}
+
+// Rank r's bulk stream behind the fat sweeps of the scale groups qs, which wrote their Z output.
+int wait_for_z(MultiCall &c, int r, const std::vector<int> &qs) {
+  MultiRank &R = c.rank(r);
+  for (int i = 0; i < c.plan.n_items(); ++i)
+    if (int rc = c.plan.item_in(i, qs) ? mwait(c.m, R, R.sb, c.swept[c.plan.fat(r)][r][i]) : IFE_OK) return rc;
+  return IFE_OK;
+}
+
+// Bulk of the differential path: per scale X level, Y level and the pointwise pass, all
+// slab-local (a chain item holds one scale, so a bulk group is one scale).
+int multi_bulk_jet(MultiCall &c) {
+  for (const std::vector<int> &qs : c.plan.bulk_groups)
+    for (int s : c.plan.bulk_scales(qs))
+      for (int r = 0; r < c.plan.W; ++r) {
+        MultiRank &R = c.rank(r);
+        const ife_volume_desc slab = c.slab(R.cut.nzl);
+        if (int rc = wait_for_z(c, r, qs)) return rc;
+        const float *zf[6];
+        for (int k = 0; k < 6; ++k) zf[k] = (const float *)R.z_out(s, k).p;
+        IFE_MCTX(c.m, R, R.bulk, ife_stage_jet_features(R.bulk, zf, c.own_mask(R), c.mask_dtype, &slab, c.sigma(s),
+                                                        c.out(R, s), c.layout));
+        if (int rc = mrecord(c.m, R, R.sb, &c.m->s_done[r][s])) return rc;
+      }
+  return IFE_OK;
+}
+
+// Bulk of the finite-difference path at rank r, the scales ss of one bulk group: X, then Y with
+// the quotient into planes 1 .. nzl of the padded buffer [nzl + 2].
+int bulk_fd_xy(MultiCall &c, int r, const std::vector<int> &ss) {
+  MultiRank &R = c.rank(r);
+  const ife_volume_desc slab = c.slab(R.cut.nzl);
+  const ZJobs z = z_jobs(c, R, ss);  // zo, sigma: the Z output of every scale and field
+  const float *xnum[IIR_MAX_JOBS], *xden[IIR_MAX_JOBS];
+  float *xo_w[IIR_MAX_JOBS], *pad1[IIR_MAX_JOBS];
+  double sg1[IIR_MAX_JOBS];
+  int nj = 0, ns = 0;
+  for (int s : ss) {
+    for (int f = 0; f < R.nf; ++f) xo_w[nj++] = (float *)R.x_out(s, f).p;
+    xnum[ns] = (const float *)R.x_out(s, 0).p;
+    xden[ns] = R.nf == 2 ? (const float *)R.x_out(s, 1).p : nullptr;
+    pad1[ns] = (float *)R.pad[s].p + c.plan.plane;
+    sg1[ns++] = c.sigma(s);
+  }
+  IFE_MCTX(c.m, R, R.bulk, ife_stage_recursive_gaussian_batch(R.bulk, nj, z.zo, xo_w, &slab, 0, z.sigma, 1));
+  if (R.nf == 2)
+    IFE_MCTX(c.m, R, R.bulk, ife_stage_recursive_gaussian_quotient(R.bulk, ns, xnum, xden, pad1, &slab, 1, sg1));
+  else
+    IFE_MCTX(c.m, R, R.bulk, ife_stage_recursive_gaussian_batch(R.bulk, ns, xnum, pad1, &slab, 1, sg1, 1));
+  return IFE_OK;
+}
+// Boundary planes of the smoothed value to the neighbours (on the sender's bulk stream, behind
+// its Y pass); from_lo[r] / from_hi[r]: behind the planes that rank r's lower / upper neighbour sent.
+int bulk_fd_halo(MultiCall &c, const std::vector<int> &ss, std::vector<hipEvent_t> &from_lo,
+                 std::vector<hipEvent_t> &from_hi) {
+  const size_t pb = (size_t)c.plan.plane * 4;
+  for (int r = 0; r < c.plan.W; ++r)
+    for (int side = 0; side < 2; ++side) {
+      const int nb = side == 0 ? r - 1 : r + 1;
+      if (nb < 0 || nb >= c.plan.W) continue;
+      MultiRank &R = c.rank(r), &N = c.rank(nb);
+      for (int s : ss) {
+        const char *mine = (const char *)R.pad[s].p + (side == 0 ? pb : (size_t)R.cut.nzl * pb);  // first / last plane
+        char *theirs = (char *)N.pad[s].p + (side == 0 ? (size_t)(N.cut.nzl + 1) * pb : 0);       // its hi / lo halo
+        if (int rc = mcopy(c.m, R, R.sb, N, theirs, mine, pb)) return rc;
+      }
+      if (int rc = mrecord(c.m, R, R.sb, side == 0 ? &from_hi[nb] : &from_lo[nb])) return rc;
+    }
+  return IFE_OK;
+}
+// The feature pass of the scales ss at rank r, behind its neighbours' planes.
+int bulk_fd_features(MultiCall &c, int r, const std::vector<int> &ss, hipEvent_t from_lo, hipEvent_t from_hi) {
+  MultiRank &R = c.rank(r);
+  const ife_volume_desc slab = c.slab(R.cut.nzl);
+  if (int rc = mwait(c.m, R, R.sb, from_lo)) return rc;
+  if (int rc = mwait(c.m, R, R.sb, from_hi)) return rc;
+  const int lo = r > 0 ? 1 : 0, hi = r < c.plan.W - 1 ? 1 : 0;
+  for (int s : ss) {
+    const float *val = (const float *)R.pad[s].p + (lo ? 0 : c.plan.plane);  // no lower neighbour: from plane 1 on
+    IFE_MCTX(c.m, R, R.bulk, ife_stage_features(R.bulk, val, nullptr, c.own_mask(R), c.mask_dtype, &slab, lo, hi,
+                                                c.out(R, s), c.layout));
+    if (int rc = mrecord(c.m, R, R.sb, &c.m->s_done[r][s])) return rc;
+  }
+  return IFE_OK;
+}
+// Bulk of the finite-difference path: X, Y (quotient), stencil planes, features, per bulk group.
+int multi_bulk_fd(MultiCall &c) {
+  const SlabPlan &p = c.plan;
+  for (const std::vector<int> &qs : p.bulk_groups) {
+    const std::vector<int> ss = p.bulk_scales(qs);
+    std::vector<hipEvent_t> from_lo(p.W, nullptr), from_hi(p.W, nullptr);
+    int rc = IFE_OK;
+    for (int r = 0; r < p.W && !rc; ++r)
+      if (!(rc = wait_for_z(c, r, qs))) rc = bulk_fd_xy(c, r, ss);
+    if (!rc) rc = bulk_fd_halo(c, ss, from_lo, from_hi);
+    for (int r = 0; r < p.W && !rc; ++r) rc = bulk_fd_features(c, r, ss, from_lo[r], from_hi[r]);
+    if (rc) return rc;
+  }
+  return IFE_OK;
+}
+
+// Everything a feature call enqueues, phase by phase; may return early with work in flight and
+// events alive -- the caller drains (multi_drain) whatever this returns.
+int multi_run(MultiCall &c) {
+  int rc = multi_check(c);
+  if (rc) return rc;
+  multi_plan(c);
+  if ((rc = multi_reserve(c)) || (rc = multi_upload(c)) || (rc = multi_prepare(c)) || (rc = multi_chains(c)))
+    return rc;
+  return c.jet() ? multi_bulk_jet(c) : multi_bulk_fd(c);
 }
 
 // The slabs of one scale back into the caller's volume (host memory), behind that scale's
 // feature launches; returns with the copies enqueued on the ranks' bulk streams.
 int multi_fetch_scale(ife_multi *m, int s, float *out) {
-  const ife_volume_desc *vol = &m->s_vol;
-  const int64_t plane = vol->nx * vol->ny, nz = vol->nz;
-  const int W = (int)m->ranks.size(), layout = m->s_layout;
-  for (int r = 0; r < W; ++r) {
-    MultiRank &R = m->ranks[(size_t)r];
+  const int64_t plane = m->s_vol.nx * m->s_vol.ny;
+  const size_t vox = (size_t)(m->s_vol.nz * plane);
+  for (size_t r = 0; r < m->ranks.size(); ++r) {
+    MultiRank &R = m->ranks[r];
     IFE_MHIP(m, hipSetDevice(R.dev));
-    const size_t slab_vox = (size_t)(R.nzl * plane);
+    const size_t slab_vox = (size_t)(R.cut.nzl * plane), first = (size_t)(R.cut.z0 * plane);
     const float *src = (const float *)R.out.p + (size_t)s * slab_vox * IFE_NUM_FEATURES;
     // on the download stream, behind this scale's feature launch only: the later scales keep
     // the bulk stream busy meanwhile
-    int rc = mwait(m, R, R.sd, m->s_done[(size_t)r][(size_t)s]);
-    if (rc) return rc;
-    if (layout == IFE_INTERLEAVED) {
-      IFE_MHIP(m, hipMemcpyAsync(out + (size_t)(R.z0 * plane) * IFE_NUM_FEATURES, src,
-                                 slab_vox * IFE_NUM_FEATURES * 4, hipMemcpyDeviceToHost, R.sd));
+    if (int rc = mwait(m, R, R.sd, m->s_done[r][(size_t)s])) return rc;
+    if (m->s_layout == IFE_INTERLEAVED) {
+      IFE_MHIP(m, hipMemcpyAsync(out + first * IFE_NUM_FEATURES, src, slab_vox * IFE_NUM_FEATURES * 4,
+                                 hipMemcpyDeviceToHost, R.sd));
     } else {
-      for (int c = 0; c < IFE_NUM_FEATURES; ++c)
-        IFE_MHIP(m, hipMemcpyAsync(out + (size_t)c * (size_t)(nz * plane) + (size_t)(R.z0 * plane),
-                                   src + (size_t)c * slab_vox, slab_vox * 4, hipMemcpyDeviceToHost, R.sd));
+      for (size_t c = 0; c < IFE_NUM_FEATURES; ++c)
+        IFE_MHIP(m, hipMemcpyAsync(out + c * vox + first, src + c * slab_vox, slab_vox * 4, hipMemcpyDeviceToHost, R.sd));
     }
   }
   return IFE_OK;
@@ -533,76 +545,64 @@ int multi_drain(ife_multi *m, bool failed) {
     if (e != hipSuccess && !failed && result == IFE_OK)
       result = mfail(m, IFE_E_HIP, "device %d: synchronisation failed: %s", R.dev, hipGetErrorString(e));
     for (auto ev : R.ev) (void)hipEventDestroy(ev);
-    R.ev.clear();
-    R.uploaded = nullptr;
+    R.ev.clear(), R.uploaded = nullptr;
   }
   (void)hipGetLastError();
   return result;
 }
 
-// The blocking calls: every scale of `path` enqueued, fetched and drained.
-int multi_features(ife_multi *m, MultiPath path, const void *image, int image_dtype, const void *mask,
-                   int mask_dtype, const ife_volume_desc *vol, const float *sigmas, int n_sigmas, float *out,
-                   int layout) {
+// The blocking calls: every scale of the call enqueued, fetched and drained.
+int multi_features(MultiCall c, float *out) {
+  ife_multi *m = c.m;
   if (!m) return IFE_E_ARG;
   if (m->streaming) return mfail(m, IFE_E_STATE, "a streaming call is in flight: ife_multi_emphysema_features_end first");
-  int rc = out ? multi_run(m, path, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout)
-               : mfail(m, IFE_E_ARG, "null pointer");
-  const size_t vox8 = rc == IFE_OK ? (size_t)(vol->nx * vol->ny * vol->nz) * IFE_NUM_FEATURES : 0;
-  for (int s = 0; s < n_sigmas && rc == IFE_OK; ++s) rc = multi_fetch_scale(m, s, out + (size_t)s * vox8);
+  int rc = out ? multi_run(c) : mfail(m, IFE_E_ARG, "null pointer");
+  const size_t vox8 = rc == IFE_OK ? (size_t)(c.plan.plane * c.plan.nz) * IFE_NUM_FEATURES : 0;
+  for (int s = 0; s < c.n_sigmas && rc == IFE_OK; ++s) rc = multi_fetch_scale(m, s, out + (size_t)s * vox8);
   const int drained = multi_drain(m, rc != IFE_OK);
   return rc != IFE_OK ? rc : drained;
 }
 
-// The _begin calls: every scale of `path` enqueued; returns once the uploads have landed.
-int multi_begin(ife_multi *m, MultiPath path, const void *image, int image_dtype, const void *mask,
-                int mask_dtype, const ife_volume_desc *vol, const float *sigmas, int n_sigmas, int layout) {
+// The _begin calls: every scale of the call enqueued; returns once the uploads have landed.
+int multi_begin(MultiCall c) {
+  ife_multi *m = c.m;
   if (!m) return IFE_E_ARG;
   if (m->streaming) return mfail(m, IFE_E_STATE, "a streaming call is already in flight");
-  int rc = multi_run(m, path, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout);
+  int rc = multi_run(c);
   for (auto &R : m->ranks) {  // the caller may reuse image and mask from here on
     if (rc != IFE_OK) break;
     hipError_t e = hipSetDevice(R.dev);
     if (e == hipSuccess && R.uploaded) e = hipEventSynchronize(R.uploaded);
     if (e != hipSuccess) rc = mfail(m, IFE_E_HIP, "device %d: upload: %s", R.dev, hipGetErrorString(e));
   }
-  if (rc != IFE_OK) {
-    (void)multi_drain(m, true);
-    return rc;
-  }
-  m->streaming = true;
-  return IFE_OK;
+  if (rc != IFE_OK) (void)multi_drain(m, true);
+  m->streaming = rc == IFE_OK;
+  return rc;
 }
 
 }  // namespace
 
 extern "C" {
 
-int ife_multi_emphysema_features(ife_multi *m, const void *image, int image_dtype, const void *mask,
-                                 int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
-                                 int n_sigmas, float *out, int layout) {
-  return multi_features(m, MULTI_FD, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, out, layout);
+int ife_multi_emphysema_features(ife_multi *m, const void *image, int image_dtype, const void *mask, int mask_dtype,
+                                 const ife_volume_desc *vol, const float *sigmas, int n_sigmas, float *out, int layout) {
+  return multi_features({m, MULTI_FD, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout}, out);
 }
 
 // ife_differential_features over several devices: the same slabs and state chains, six Z jobs per
 // scale, and behind them only slab-local work (multi_run, MULTI_JET).
-int ife_multi_differential_features(ife_multi *m, const void *image, int image_dtype, const void *mask,
-                                    int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
-                                    int n_sigmas, float *out, int layout) {
-  return multi_features(m, MULTI_JET, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, out, layout);
+int ife_multi_differential_features(ife_multi *m, const void *image, int image_dtype, const void *mask, int mask_dtype,
+                                    const ife_volume_desc *vol, const float *sigmas, int n_sigmas, float *out, int layout) {
+  return multi_features({m, MULTI_JET, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout}, out);
 }
 
-// The scale loop of tools/ExtractFeatures.cxx:132-154 over several devices, one scale at a time
-// to the host: _begin uploads the slabs once, runs the prepass once and enqueues EVERY scale on
-// every device (nothing is waited for); _fetch(k) blocks until scale k of every slab has been
-// copied into `out` (the whole volume of that scale, host memory) while the later scales keep
-// computing; _end drains.  The inputs may be reused once _begin returns: it waits for the uploads
-// (from page-locked memory they run asynchronously to the host), not for the scales; `out` must
-// stay valid until its _fetch returns.
-int ife_multi_emphysema_features_begin(ife_multi *m, const void *image, int image_dtype, const void *mask,
-                                       int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
-                                       int n_sigmas, int layout) {
-  return multi_begin(m, MULTI_FD, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout);
+// The scale loop over several devices, one scale at a time to the host (ife_hip.h): _begin enqueues
+// EVERY scale on every device and waits for the uploads only (from page-locked memory they run
+// asynchronously to the host), so the inputs may be reused once it returns; `out` must stay valid
+// until its _fetch returns.
+int ife_multi_emphysema_features_begin(ife_multi *m, const void *image, int image_dtype, const void *mask, int mask_dtype,
+                                       const ife_volume_desc *vol, const float *sigmas, int n_sigmas, int layout) {
+  return multi_begin({m, MULTI_FD, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout});
 }
 
 // The same stream with every scale that of ife_multi_differential_features; _fetch and _end are
@@ -610,7 +610,7 @@ int ife_multi_emphysema_features_begin(ife_multi *m, const void *image, int imag
 int ife_multi_differential_features_begin(ife_multi *m, const void *image, int image_dtype, const void *mask,
                                           int mask_dtype, const ife_volume_desc *vol, const float *sigmas,
                                           int n_sigmas, int layout) {
-  return multi_begin(m, MULTI_JET, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout);
+  return multi_begin({m, MULTI_JET, image, image_dtype, mask, mask_dtype, vol, sigmas, n_sigmas, layout});
 }
 
 int ife_multi_emphysema_features_fetch(ife_multi *m, int scale, float *out) {

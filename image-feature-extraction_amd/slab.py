@@ -10,7 +10,7 @@ Everything is slab-local except two things:
 
   * the Z recursion of ITK's recursive Gaussian, which runs the full length of every Z
     line.  It is kept exactly sequential by handing the recursion STATE across the slab
-    boundaries (C-ABI `ife_stage_z_sweep` / `ife_stage_z_combine`): the causal chain
+    boundaries (C-ABI `ife_stage_z_sweep` / `ife_stage_z_fused`): the causal chain
     travels rank 0 -> W-1, the anticausal chain W-1 -> 0, both at once, as records of
     4 doubles per line and (scale, field): the last four outputs of the recursion.  The
     input samples such a state refers to do not travel: a rank's slab of the RAW data is
@@ -72,6 +72,45 @@ def slab_bounds(nz, world):
     return b
 
 
+def slab_plan(lines, world, n_scales, jobs_per_scale, line_groups=None, scales_per_item=None, max_jobs=8):
+    """(groups, scale_groups, items, bulk_groups) of a plane of `lines` Z lines over `world` ranks:
+    the rules of csrc/slab_plan.hpp, which tests/test_slab_plan_cpu.py holds equal to these.
+    groups: (line0, nlines) of the boundary chains; scale_groups: the scales whose sweeps share a
+    launch and a message; items: (scale group, line group); bulk_groups: the scale groups whose
+    bulk work shares launches.  max_jobs: jobs of one launch (IIR_MAX_JOBS)."""
+    # line groups pipeline a boundary: the transfer of one group travels while the next is
+    # swept, and a chain's start-up (W-1 hops of kernel + wire + latency) shrinks with the
+    # item.  Four groups carrying all scales at every world size: with 50 MB per boundary and
+    # direction (512^2, 3 scales, 2 fields) an item is 12.6 MB, a chain of eight ranks takes
+    # 7 x (0.18 ms of wire at 70 GB/s + kernel + latency) + 3 x 0.18 = 2.4 ms from its first
+    # sweep to its last state -- hidden behind the `depth` steps the engine keeps in flight -- at
+    # 16 point-to-point calls and 8 chain launches per rank and step.  (Round 2 ran eight
+    # ranks with one scale per item and three groups, 36 calls: the host thread then needs
+    # about as long per step as the device, scripts/experiments/slab_p2p_host_time.py.)
+    G = line_groups if line_groups is not None else (1 if world == 1 else 4)
+    G = max(1, min(G, (lines + 255) // 256))
+    per = ((lines + G - 1) // G + 255) // 256 * 256  # whole workgroups of 256 lines
+    groups = [(l0, min(lines, l0 + per) - l0) for l0 in range(0, lines, per)]
+    max_scales = max(1, max_jobs // jobs_per_scale)   # scales of one launch
+    spi = scales_per_item if scales_per_item else n_scales
+    spi = max(1, min(spi, max_scales, n_scales))
+    # scale groups: their sweeps share launches and messages; the bulk phase follows them
+    scale_groups = [list(range(s0, min(n_scales, s0 + spi))) for s0 in range(0, n_scales, spi)]
+    items = [(q, g) for q in range(len(scale_groups)) for g in range(len(groups))]
+    # the bulk phase follows the chains group by group, except that everything behind the
+    # first group is merged into launches of up to `max_jobs` jobs: a one-scale launch on a
+    # thin slab fills a third of the device (64 planes: 0.122 ms per scale against 0.29 for three)
+    bulk_groups = [[0]]
+    for q in range(1, len(scale_groups)):
+        last = bulk_groups[-1]
+        n_sc = sum(len(scale_groups[k]) for k in last) + len(scale_groups[q])
+        if len(bulk_groups) > 1 and n_sc <= max_scales:
+            last.append(q)
+        else:
+            bulk_groups.append([q])
+    return groups, scale_groups, items, bulk_groups
+
+
 def sweep_schedule(rank, world, n_items):
     """[(direction, item)] in the order this rank runs its sweeps (module docstring)."""
     ev = []
@@ -129,13 +168,6 @@ class HipStages:
         self.ctx.stage_recursive_gaussian_quotient([t.data_ptr() for t in nums], [t.data_ptr() for t in dens],
                                                    [t.data_ptr() for t in dsts], tuple(dsts[0].shape),
                                                    spacing, axis, sigmas)
-
-    def z_combine(self, srcs_ext, pad_lo, nzl, dsts, spacing, sigmas, has_lo, has_hi, cks):
-        own = [t[pad_lo:pad_lo + nzl] for t in srcs_ext]
-        shape = tuple(own[0].shape)
-        self.ctx.stage_z_combine([t.data_ptr() for t in own], [t.data_ptr() for t in dsts], shape,
-                                 spacing, 0, shape[1] * shape[2], sigmas, has_lo, has_hi,
-                                 [c.data_ptr() for c in cks])
 
     def gaussian_axis_batch(self, srcs, dsts, spacing, axis, sigmas):
         """One launch over several float volumes (jobs) shaped like dsts[0]."""
@@ -375,37 +407,8 @@ class SlabEngine:
         self.has_mask = has_mask
         self.nf = nf = 2 if has_mask else 1
         S = len(self.sigmas)
-        L = ny * nx
-        # line groups pipeline a boundary: the transfer of one group travels while the next is
-        # swept, and a chain's start-up (W-1 hops of kernel + wire + latency) shrinks with the
-        # item.  Four groups carrying all scales at every world size: with 50 MB per boundary and
-        # direction (512^2, 3 scales, 2 fields) an item is 12.6 MB, a chain of eight ranks takes
-        # 7 x (0.18 ms of wire at 70 GB/s + kernel + latency) + 3 x 0.18 = 2.4 ms from its first
-        # sweep to its last state -- hidden behind the `depth` steps the engine keeps in flight -- at
-        # 16 point-to-point calls and 8 chain launches per rank and step.  (Round 2 ran eight
-        # ranks with one scale per item and three groups, 36 calls: the host thread then needs
-        # about as long per step as the device, scripts/experiments/slab_p2p_host_time.py.)
-        G = line_groups if line_groups is not None else (1 if world == 1 else 4)
-        G = max(1, min(G, (L + 255) // 256))
-        per = ((L + G - 1) // G + 255) // 256 * 256  # whole workgroups of 256 lines
-        self.groups = [(l0, min(L, l0 + per) - l0) for l0 in range(0, L, per)]
-        max_jobs = max(1, 8 // nf)                     # jobs of one launch (IIR_MAX_JOBS = 8)
-        spi = scales_per_item if scales_per_item else S
-        spi = max(1, min(spi, max_jobs, S))
-        # scale groups: their sweeps share launches and messages; the bulk phase follows them
-        self.scale_groups = [list(range(s0, min(S, s0 + spi))) for s0 in range(0, S, spi)]
-        self.items = [(q, g) for q in range(len(self.scale_groups)) for g in range(len(self.groups))]
-        # the bulk phase follows the chains group by group, except that everything behind the
-        # first group is merged into launches of up to `max_jobs` jobs: a one-scale launch on a
-        # thin slab fills a third of the device (64 planes: 0.122 ms per scale against 0.29 for three)
-        self.bulk_groups = [[0]]
-        for q in range(1, len(self.scale_groups)):
-            last = self.bulk_groups[-1]
-            n_sc = sum(len(self.scale_groups[k]) for k in last) + len(self.scale_groups[q])
-            if len(self.bulk_groups) > 1 and n_sc <= max_jobs:
-                last.append(q)
-            else:
-                self.bulk_groups.append([q])
+        self.groups, self.scale_groups, self.items, self.bulk_groups = slab_plan(
+            ny * nx, world, S, nf, line_groups=line_groups, scales_per_item=scales_per_item)
         self.schedule = sweep_schedule(rank, world, len(self.items))
         f = lambda *shp: alloc(shp, "float32")
         self.pad_lo, self.pad_hi = overlap(rank, world)

@@ -151,17 +151,6 @@ class OracleStages:
                 q = np.where(d != 0, n / np.where(d != 0, d, 1), np.finfo(np.float32).max).astype(np.float32)
             dst.copy_(torch.from_numpy(q))
 
-    def z_combine(self, srcs_ext, pad_lo, nzl, dsts, spacing, sigmas, has_lo, has_hi, cks):
-        import torch
-        for k, dst in enumerate(dsts):
-            nzl, ny, nx = dst.shape
-            res = np.empty((nzl, ny * nx), np.float32)
-            for (ptr, d, l0), v in list(self.store.items()):
-                if ptr == cks[k].data_ptr() and d == 0:
-                    w = self.store[(ptr, 1, l0)]
-                    res[:, l0:l0 + v.shape[1]] = (v + w).astype(np.float32)
-            dst.copy_(torch.from_numpy(res.reshape(nzl, ny, nx)))
-
     def gaussian_axis_batch(self, srcs, dsts, spacing, axis, sigmas):
         import torch
         for src, dst, sigma in zip(srcs, dsts, sigmas):
