@@ -32,6 +32,7 @@ OPT_FEAT_RING = 10
 OPT_DENSE_SCRATCH_MB = 11
 OPT_Z_SWEEP = 12
 OPT_DIFFERENTIAL = 13  # 1: the composite calls take their features from the jet (include/ife_hip.h)
+INTERP_LINEAR, INTERP_NEAREST = 0, 1  # ife_interp: interpolation of ife_resample
 BAG_COUNTS, BAG_FREQUENCIES = 0, 1  # ife_bag_values: what the dense bag stream delivers
 Z_STATE_BYTES = 32   # IFE_Z_STATE_BYTES: one state record of the slab Z pass, per line and job
 Z_OVERLAP_LO, Z_OVERLAP_HI = 3, 4  # IFE_Z_OVERLAP_*: neighbour planes around a slab's input
@@ -67,6 +68,7 @@ EXPORTS = (
     "ife_deflate_bound", "ife_deflate", "ife_emphysema_features_fetch_deflated",
     "ife_stage_z_sweep_order", "ife_stage_z_combine_order", "ife_stage_z_fused_order",
     "ife_stage_jet_features", "ife_multi_differential_features", "ife_multi_differential_features_begin",
+    "ife_resample", "ife_resample_f64",
 )
 
 
@@ -211,6 +213,9 @@ def load_library():
                                 C.POINTER(C.c_uint32), i32]
     lib.ife_emphysema_features_fetch_deflated.argtypes = [vp, i32, i32, vp, C.c_size_t,
                                                           C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]
+    d3 = C.POINTER(C.c_double)
+    lib.ife_resample.argtypes = [vp, vp, i32, vd, d3, vd, d3, d3, i32, C.c_double, vp, i32]
+    lib.ife_resample_f64.argtypes = [vp, vp, vd, d3, vd, d3, d3, i32, C.c_double, vp, i32]
     _lib = lib
     return lib
 
@@ -223,6 +228,7 @@ def _desc(shape_zyx, spacing_xyz):
 
 _IMG_DT = {np.dtype(np.float32): F32, np.dtype(np.int16): I16}
 _MSK_DT = {np.dtype(np.uint8): U8, np.dtype(np.uint16): U16}
+_RESAMPLE_DT = {**_IMG_DT, **_MSK_DT}   # what ife_resample reads; float64 goes to ife_resample_f64
 
 
 def _image_arg(image):
@@ -589,6 +595,45 @@ class Context:
         self._chk(self._lib.ife_expected_distance(
             self._h, mptr, mdt, prob.ctypes.data, C.byref(d), C.byref(value), C.byref(n), MEM_HOST))
         return value.value, n.value
+
+    # ---- resampling onto a target grid ---------------------------------------------
+    def _resample(self, src_ptr, src_dtype, src_shape, src_spacing, src_origin, dst_shape, dst_spacing,
+                  dst_origin, translation, interpolation, default, out_ptr, mem):
+        sd, dd = _desc(src_shape, src_spacing), _desc(dst_shape, dst_spacing)
+        geom = (C.byref(sd), _double_array(src_origin), C.byref(dd), _double_array(dst_origin),
+                _double_array(translation), int(interpolation), float(default), C.c_void_p(out_ptr or 0), mem)
+        if src_dtype is None:
+            self._chk(self._lib.ife_resample_f64(self._h, C.c_void_p(src_ptr or 0), *geom))
+        else:
+            self._chk(self._lib.ife_resample(self._h, C.c_void_p(src_ptr or 0), int(src_dtype), *geom))
+
+    def resample(self, src, src_spacing, src_origin, dst_shape, dst_spacing, dst_origin,
+                 translation=(0, 0, 0), interpolation=INTERP_LINEAR, default=0.0):
+        """src [z, y, x] on the grid (dst_shape (nz, ny, nx), dst_spacing, dst_origin); spacings,
+        origins and the translation are (x, y, z).  float64 in gives float64 out; float32, int16,
+        uint8 and uint16 give float32 (linear) or their own dtype (nearest)."""
+        src = np.ascontiguousarray(src)
+        if src.ndim != 3:
+            raise ValueError("src must have three dimensions")
+        if src.dtype == np.float64:
+            dt, odt = None, np.float64
+        elif src.dtype in _RESAMPLE_DT:
+            dt = _RESAMPLE_DT[src.dtype]
+            odt = np.float32 if interpolation == INTERP_LINEAR else src.dtype
+        else:
+            raise TypeError("src must be float64, float32, int16, uint8 or uint16")
+        out = np.empty(tuple(int(v) for v in dst_shape), odt)
+        self._resample(src.ctypes.data, dt, src.shape, src_spacing, src_origin, out.shape, dst_spacing,
+                       dst_origin, translation, interpolation, default, out.ctypes.data, MEM_HOST)
+        return out
+
+    def resample_device(self, src_ptr, src_dtype, src_shape, src_spacing, src_origin, dst_shape,
+                        dst_spacing, dst_origin, out_ptr, translation=(0, 0, 0),
+                        interpolation=INTERP_LINEAR, default=0.0):
+        """Enqueues on the context's stream.  src_dtype None: float64 in and out
+        (ife_resample_f64); else out_ptr is float32 (linear) or the source's type (nearest)."""
+        self._resample(src_ptr, src_dtype, src_shape, src_spacing, src_origin, dst_shape, dst_spacing,
+                       dst_origin, translation, interpolation, default, out_ptr, MEM_DEVICE)
 
     # ---- device-pointer entry points (inputs already in HBM) ------------------
     def signed_distance_map_device(self, mask_ptr, mask_dtype, shape_zyx, spacing, out_ptr,

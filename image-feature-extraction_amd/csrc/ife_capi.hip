@@ -26,6 +26,7 @@
 #include "dense_kernels.hpp"
 #include "dense_plan.hpp"
 #include "deflate_kernels.hpp"
+#include "resample_kernels.hpp"
 #define IFE_IIR_NS iir_exact
 #define IFE_IIR_FMA 0
 #include "iir_kernels.inc"
@@ -200,6 +201,11 @@ struct ife_ctx {
   // DEFLATE on the device (deflate_capi.inc): offsets, counts and CRC pieces of the chunks, and the
   // blocks of a plane of the stream on their way to the host
   DevBuf df_ws, df_out;
+  // resampling (resample_capi.inc): the three axis tables on the device, their host copy (which
+  // an upload in flight still reads) and the event behind that upload
+  DevBuf rs_tab;
+  std::vector<ResampleEntry> rs_host;
+  hipEvent_t rs_up = nullptr;
   std::vector<ProfRec> prof;
   std::vector<hipEvent_t> ev_pool;
   double acc_ms[KK_COUNT] = {0};
@@ -1069,6 +1075,7 @@ void ife_ctx_destroy(ife_ctx *ctx) {
   if (ctx->sc_copy) (void)hipStreamDestroy(ctx->sc_copy);
   dense_stream_release(ctx);
   if (ctx->ds.copy) (void)hipStreamDestroy(ctx->ds.copy);
+  if (ctx->rs_up) (void)hipEventDestroy(ctx->rs_up);
   for (auto &r : ctx->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
   for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
   delete ctx;  // every DevBuf of the context frees itself here, behind the events and streams
@@ -1592,5 +1599,6 @@ int ife_reset_kernel_times(ife_ctx *ctx) {
 #include "deflate_capi.inc"  // reads the scale stream
 #include "stats_capi.inc"
 #include "distance_capi.inc"
+#include "resample_capi.inc"
 #include "dense_capi.inc"
 #include "multi_capi.inc"

@@ -78,6 +78,15 @@ struct Spacing3 {
   double &operator[](size_t i) { return v[i]; }
   const double &operator[](size_t i) const { return v[i]; }
 };
+inline std::ostream &operator<<(std::ostream &os, const Spacing3 &s) {  // as itk::Point and itk::Vector print
+  return os << "[" << s[0] << ", " << s[1] << ", " << s[2] << "]";
+}
+// itk::Image::GetDirection(): always the identity here (direction cosines are not carried; the
+// file's own geometry travels in FileGeometry)
+struct Direction3 {};
+inline std::ostream &operator<<(std::ostream &os, const Direction3 &) {  // as itk::Matrix prints
+  return os << "1 0 0\n0 1 0\n0 0 1\n";
+}
 struct Region3 {  // itk::ImageRegion<3>: index + size
   typedef Size3 SizeType;
   typedef Index3 IndexType;
@@ -128,6 +137,7 @@ class ImageBase3 {
   const Spacing3 &GetSpacing() const { return spacing_; }
   void SetOrigin(const Spacing3 &o) { origin_ = o; }
   const Spacing3 &GetOrigin() const { return origin_; }
+  Direction3 GetDirection() const { return Direction3(); }
   void SetFileGeometry(const FileGeometry &g) { geom_ = g; }
   const FileGeometry &GetFileGeometry() const { return geom_; }
   void CopyInformation(const ImageBase3 *o) {

@@ -732,6 +732,67 @@ int ife_signed_distance_map(ife_ctx *ctx, const void *mask, int mask_dtype,
 int ife_expected_distance(ife_ctx *ctx, const void *mask, int mask_dtype, const double *prob,
                           const ife_volume_desc *vol, double *result, int64_t *n_inside, int mem);
 
+/* ---- resampling onto a target grid (tools/Resample.cxx:83-99) ------------------------------ *
+ *
+ * itk::ResampleImageFilter with an itk::TranslationTransform, linear or nearest-neighbour
+ * interpolation.  Parity with ITK is unpinned (ITK's index-from-point matrix comes out of an SVD
+ * inverse and its scan-line shortcut differs between versions); the arithmetic below is this
+ * library's own and is normative.  Direction cosines are ignored, as on the whole hot path:
+ * geometry is size, spacing and origin per axis, and the transform is axis-aligned, so everything
+ * about an output voxel's position factors per axis.  All arithmetic is in double and every
+ * operation rounds on its own.
+ *
+ * Per axis, for output index i in [0, n_t), with the source axis (n_s, s_s, O_s), the output axis
+ * (n_t, s_t, O_t) and the translation T:
+ *   p = O_t + (double)i * s_t             output point
+ *   q = p + T                             TranslationTransform: point + offset
+ *   c = (q - O_s) / s_s                   continuous index in the source
+ *   inside = (c >= -0.5) && (c < (n_s - 1) + 0.5)        a NaN compares false: outside
+ * and only where inside (nothing outside is ever converted to an integer):
+ *   b = floor(c); if (b < 0) b = 0        c in [-0.5, 0) gives b = 0 and t < 0
+ *   t = c - (double)b
+ *   skip = (t <= 0) || (b + 1 > n_s - 1)
+ *   near = min(floor(c + 0.5), n_s - 1)   the min bounds memory: n_s = 1, c = nextafter(0.5, 0)
+ * A voxel is inside when all three axes are; every other voxel gets default_value.
+ *
+ * IFE_INTERP_LINEAR: with L(a, b, t, skip) = skip ? a : a + (b - a) * t -- a select, so a skipped
+ * axis hands `a` on untouched (infinities, NaN payloads) and never reads the upper neighbour --
+ * and v000 the source voxel at (b_x, b_y, b_z), nested x, then y, then z:
+ *   vx00 = L(v000, v100, t_x, skip_x)     likewise vx10, vx01, vx11
+ *   vxy0 = L(vx00, vx10, t_y, skip_y)     vxy1 = L(vx01, vx11, t_y, skip_y)
+ *   v    = L(vxy0, vxy1, t_z, skip_z)
+ * (the nesting of itk::LinearInterpolateImageFunction::EvaluateOptimized in three dimensions,
+ * its early exits "distance <= 0" and "neighbour beyond the end index" as the skip rule).  Within
+ * half a voxel of the border the edge value is extended.
+ * IFE_INTERP_NEAREST: the source voxel at (near_x, near_y, near_z).
+ *
+ * A grid resampled onto itself comes back bit for bit where spacing and origin are dyadic; with a
+ * spacing such as 0.7, c is i +- a few ulp and a voxel may come out as
+ * v[i-1] + (v[i] - v[i-1]) * (1 - eps) (relative difference about 1e-13 on random data).  The
+ * 2^-26 truncation with which old ITK hid this is not reproduced.
+ *
+ * ife_resample reads IFE_F32, IFE_I16, IFE_U8 and IFE_U16.  Linear writes float: the value is
+ * formed in double and rounded once.  Nearest writes the source's own type (labels stay labels).
+ * ife_resample_f64 is double in, double out (the reference tool's pixel type).
+ * Refused with IFE_E_ARG before anything is written: a null pointer; an unknown dtype or
+ * interpolation; a non-finite origin, translation or default value; a default value that is not
+ * exactly a value of the output type; IFE_MEM_DEVICE pointers not aligned to their element size;
+ * source and output ranges that overlap; a spacing that is not positive.  IFE_E_SIZE: a
+ * non-positive size.  Source axes of length 1 are legal (every voxel skips that axis).  Origins,
+ * the translation and the descriptors are HOST arrays; src and out follow `mem`.  Runs on the
+ * context's stream; one device. */
+typedef enum { IFE_INTERP_LINEAR = 0, IFE_INTERP_NEAREST = 1 } ife_interp;
+
+int ife_resample(ife_ctx *ctx, const void *src, int src_dtype, const ife_volume_desc *src_vol,
+                 const double src_origin[3], const ife_volume_desc *dst_vol,
+                 const double dst_origin[3], const double translation[3], int interpolation,
+                 double default_value, void *out, int mem);
+
+int ife_resample_f64(ife_ctx *ctx, const double *src, const ife_volume_desc *src_vol,
+                     const double src_origin[3], const ife_volume_desc *dst_vol,
+                     const double dst_origin[3], const double translation[3], int interpolation,
+                     double default_value, double *out, int mem);
+
 /* ---- measurement ------------------------------------------------------------------- */
 
 #define IFE_MAX_KERNEL_KINDS 24
