@@ -33,6 +33,7 @@ OPT_DENSE_SCRATCH_MB = 11
 OPT_Z_SWEEP = 12
 OPT_DIFFERENTIAL = 13  # 1: the composite calls take their features from the jet (include/ife_hip.h)
 INTERP_LINEAR, INTERP_NEAREST = 0, 1  # ife_interp: interpolation of ife_resample
+BSPLINE_MAX_ORDER = 5  # ife_bspline_coefficients / ife_resample_bspline: orders 0 .. 5
 BAG_COUNTS, BAG_FREQUENCIES = 0, 1  # ife_bag_values: what the dense bag stream delivers
 Z_STATE_BYTES = 32   # IFE_Z_STATE_BYTES: one state record of the slab Z pass, per line and job
 Z_OVERLAP_LO, Z_OVERLAP_HI = 3, 4  # IFE_Z_OVERLAP_*: neighbour planes around a slab's input
@@ -69,6 +70,8 @@ EXPORTS = (
     "ife_stage_z_sweep_order", "ife_stage_z_combine_order", "ife_stage_z_fused_order",
     "ife_stage_jet_features", "ife_multi_differential_features", "ife_multi_differential_features_begin",
     "ife_resample", "ife_resample_f64",
+    "ife_bspline_coefficients", "ife_bspline_coefficients_f64", "ife_resample_bspline",
+    "ife_resample_bspline_f64", "ife_window_u8",
 )
 
 
@@ -216,6 +219,11 @@ def load_library():
     d3 = C.POINTER(C.c_double)
     lib.ife_resample.argtypes = [vp, vp, i32, vd, d3, vd, d3, d3, i32, C.c_double, vp, i32]
     lib.ife_resample_f64.argtypes = [vp, vp, vd, d3, vd, d3, d3, i32, C.c_double, vp, i32]
+    lib.ife_bspline_coefficients.argtypes = [vp, vp, i32, vd, i32, vp, i32]
+    lib.ife_bspline_coefficients_f64.argtypes = [vp, vp, vd, i32, vp, i32]
+    lib.ife_resample_bspline.argtypes = [vp, vp, i32, vd, d3, vd, d3, d3, i32, i32, C.c_double, vp, i32]
+    lib.ife_resample_bspline_f64.argtypes = [vp, vp, vd, d3, vd, d3, d3, i32, i32, C.c_double, vp, i32]
+    lib.ife_window_u8.argtypes = [vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_uint8, C.c_uint8, vp, i32]
     _lib = lib
     return lib
 
@@ -634,6 +642,97 @@ class Context:
         (ife_resample_f64); else out_ptr is float32 (linear) or the source's type (nearest)."""
         self._resample(src_ptr, src_dtype, src_shape, src_spacing, src_origin, dst_shape, dst_spacing,
                        dst_origin, translation, interpolation, default, out_ptr, MEM_DEVICE)
+
+    # ---- B-spline resampling (orders 0 to 5) and the 8-bit window -------------------
+    @staticmethod
+    def _bspline_source(src):
+        src = np.ascontiguousarray(src)
+        if src.ndim != 3:
+            raise ValueError("src must have three dimensions")
+        if src.dtype == np.float64:
+            return src, None
+        if src.dtype not in _RESAMPLE_DT:
+            raise TypeError("src must be float64, float32, int16, uint8 or uint16")
+        return src, _RESAMPLE_DT[src.dtype]
+
+    def bspline_coefficients_device(self, src_ptr, src_dtype, shape_zyx, order, coef_ptr):
+        """Enqueues on the context's stream; coef_ptr: float64 [z, y, x] in device memory.
+        src_dtype None: float64 source (ife_bspline_coefficients_f64), where coef_ptr may equal
+        src_ptr (in place)."""
+        d = _desc(shape_zyx, (1.0, 1.0, 1.0))
+        if src_dtype is None:
+            self._chk(self._lib.ife_bspline_coefficients_f64(self._h, C.c_void_p(src_ptr or 0), C.byref(d),
+                                                             int(order), C.c_void_p(coef_ptr or 0), MEM_DEVICE))
+        else:
+            self._chk(self._lib.ife_bspline_coefficients(self._h, C.c_void_p(src_ptr or 0), int(src_dtype),
+                                                         C.byref(d), int(order), C.c_void_p(coef_ptr or 0),
+                                                         MEM_DEVICE))
+
+    def bspline_coefficients(self, src, order=3):
+        """The B-spline coefficients of src [z, y, x] (float64, float32, int16, uint8 or uint16)
+        for `order` in 0..5, as float64 (include/ife_hip.h states the arithmetic)."""
+        src, dt = self._bspline_source(src)
+        coef = np.empty(src.shape, np.float64)
+        d = _desc(src.shape, (1.0, 1.0, 1.0))
+        if dt is None:
+            self._chk(self._lib.ife_bspline_coefficients_f64(self._h, src.ctypes.data, C.byref(d), int(order),
+                                                             coef.ctypes.data, MEM_HOST))
+        else:
+            self._chk(self._lib.ife_bspline_coefficients(self._h, src.ctypes.data, dt, C.byref(d), int(order),
+                                                         coef.ctypes.data, MEM_HOST))
+        return coef
+
+    def _resample_bspline(self, src_ptr, src_dtype, src_shape, src_spacing, src_origin, dst_shape, dst_spacing,
+                          dst_origin, translation, order, extrapolate, default, out_ptr, mem):
+        sd, dd = _desc(src_shape, src_spacing), _desc(dst_shape, dst_spacing)
+        geom = (C.byref(sd), _double_array(src_origin), C.byref(dd), _double_array(dst_origin),
+                _double_array(translation), int(order), int(extrapolate), float(default),
+                C.c_void_p(out_ptr or 0), mem)
+        if src_dtype is None:
+            self._chk(self._lib.ife_resample_bspline_f64(self._h, C.c_void_p(src_ptr or 0), *geom))
+        else:
+            self._chk(self._lib.ife_resample_bspline(self._h, C.c_void_p(src_ptr or 0), int(src_dtype), *geom))
+
+    def resample_bspline(self, src, src_spacing, src_origin, dst_shape, dst_spacing, dst_origin,
+                         translation=(0, 0, 0), order=3, extrapolate=False, default=0.0):
+        """src [z, y, x] on the grid (dst_shape (nz, ny, nx), dst_spacing, dst_origin) through a
+        B-spline of `order` 0..5; spacings, origins and the translation are (x, y, z).  Outside
+        voxels get `default`, or with extrapolate the nearest source voxel.  float64 in gives
+        float64 out; float32, int16, uint8 and uint16 give float32."""
+        src, dt = self._bspline_source(src)
+        out = np.empty(tuple(int(v) for v in dst_shape), np.float64 if dt is None else np.float32)
+        self._resample_bspline(src.ctypes.data, dt, src.shape, src_spacing, src_origin, out.shape, dst_spacing,
+                               dst_origin, translation, order, extrapolate, default, out.ctypes.data, MEM_HOST)
+        return out
+
+    def resample_bspline_device(self, src_ptr, src_dtype, src_shape, src_spacing, src_origin, dst_shape,
+                                dst_spacing, dst_origin, out_ptr, translation=(0, 0, 0), order=3,
+                                extrapolate=False, default=0.0):
+        """Enqueues on the context's stream.  src_dtype None: float64 in and out
+        (ife_resample_bspline_f64); else out_ptr is float32."""
+        self._resample_bspline(src_ptr, src_dtype, src_shape, src_spacing, src_origin, dst_shape, dst_spacing,
+                               dst_origin, translation, order, extrapolate, default, out_ptr, MEM_DEVICE)
+
+    def window_u8_device(self, src_ptr, mask_ptr, n, window_min, window_max, out_ptr, out_min=0, out_max=255):
+        """Enqueues on the context's stream; src_ptr and mask_ptr (0: no mask): n float64,
+        out_ptr: n uint8, all in device memory."""
+        self._chk(self._lib.ife_window_u8(self._h, C.c_void_p(src_ptr or 0), C.c_void_p(mask_ptr or 0), int(n),
+                                          float(window_min), float(window_max), int(out_min), int(out_max),
+                                          C.c_void_p(out_ptr or 0), MEM_DEVICE))
+
+    def window_u8(self, src, window_min, window_max, mask=None, out_min=0, out_max=255):
+        """float64 values windowed to uint8: below window_min out_min, above window_max out_max,
+        linear between (truncated); where a float64 mask of the same shape is 0 the result is 0."""
+        src = np.ascontiguousarray(src, np.float64)
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.float64)
+            if mask.shape != src.shape:
+                raise ValueError("mask and src differ in shape")
+        out = np.empty(src.shape, np.uint8)
+        self._chk(self._lib.ife_window_u8(self._h, src.ctypes.data, None if mask is None else mask.ctypes.data,
+                                          src.size, float(window_min), float(window_max), int(out_min),
+                                          int(out_max), out.ctypes.data, MEM_HOST))
+        return out
 
     # ---- device-pointer entry points (inputs already in HBM) ------------------
     def signed_distance_map_device(self, mask_ptr, mask_dtype, shape_zyx, spacing, out_ptr,

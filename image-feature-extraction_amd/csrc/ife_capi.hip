@@ -27,6 +27,7 @@
 #include "dense_plan.hpp"
 #include "deflate_kernels.hpp"
 #include "resample_kernels.hpp"
+#include "bspline_kernels.hpp"
 #define IFE_IIR_NS iir_exact
 #define IFE_IIR_FMA 0
 #include "iir_kernels.inc"
@@ -206,6 +207,11 @@ struct ife_ctx {
   DevBuf rs_tab;
   std::vector<ResampleEntry> rs_host;
   hipEvent_t rs_up = nullptr;
+  // B-spline resampling (bspline_capi.inc): the coefficients of the source (8 bytes per voxel), the
+  // gather's tables on the device, their host copy and the event behind its upload
+  DevBuf bs_coef, bs_tab;
+  std::vector<double> bs_host;
+  hipEvent_t bs_up = nullptr;
   std::vector<ProfRec> prof;
   std::vector<hipEvent_t> ev_pool;
   double acc_ms[KK_COUNT] = {0};
@@ -1076,6 +1082,7 @@ void ife_ctx_destroy(ife_ctx *ctx) {
   dense_stream_release(ctx);
   if (ctx->ds.copy) (void)hipStreamDestroy(ctx->ds.copy);
   if (ctx->rs_up) (void)hipEventDestroy(ctx->rs_up);
+  if (ctx->bs_up) (void)hipEventDestroy(ctx->bs_up);
   for (auto &r : ctx->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
   for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
   delete ctx;  // every DevBuf of the context frees itself here, behind the events and streams
@@ -1600,5 +1607,6 @@ int ife_reset_kernel_times(ife_ctx *ctx) {
 #include "stats_capi.inc"
 #include "distance_capi.inc"
 #include "resample_capi.inc"
+#include "bspline_capi.inc"  // shares the resampling checks
 #include "dense_capi.inc"
 #include "multi_capi.inc"

@@ -793,6 +793,96 @@ int ife_resample_f64(ife_ctx *ctx, const double *src, const ife_volume_desc *src
                      const double dst_origin[3], const double translation[3], int interpolation,
                      double default_value, double *out, int mem);
 
+/* ---- B-spline resampling, orders 0 to 5, and the 8-bit window (tools/ExtractWindow.cxx) ------ *
+ *
+ * itk::BSplineInterpolateImageFunction behind itk::ResampleImageFilter, then
+ * itk::IntensityWindowingImageFilter.  Parity with ITK is unpinned, as for ife_resample; the
+ * arithmetic below is normative.  It follows ITK's BSplineDecompositionImageFilter and
+ * BSplineInterpolateImageFunction except where marked "ours".  Everything is in double and every
+ * operation rounds on its own.
+ *
+ * Poles z (computed on the host) and horizons h = ceil(log(1e-10) / log|z|):
+ *   order 2: sqrt(8)-3                                                        h = 14
+ *   order 3: sqrt(3)-2                                                        h = 18
+ *   order 4: sqrt(664-sqrt(438976))+sqrt(304)-19, sqrt(664+sqrt(438976))-sqrt(304)-19    h = 23, 6
+ *   order 5: sqrt(135/2-sqrt(17745/4))+sqrt(105/4)-13/2,
+ *            sqrt(135/2+sqrt(17745/4))-sqrt(105/4)-13/2                       h = 28, 8
+ * Orders 0 and 1 have no poles: the coefficients are the source converted to double.
+ *
+ * Prefilter: the axes run x, then y, then z, each pass in place.  A line of length N = 1 is left
+ * untouched (no gain).  Otherwise, per line c[0 .. N-1]:
+ *   g = 1; for each pole z: g = g*(1-z)*(1-1/z);   c[n] = c[n]*g for every n
+ *   then for each pole z, in the order above:
+ *     causal start, h < N:   zn = z; s = c[0]; for n = 1..h-1: { s = s + zn*c[n]; zn = zn*z; }
+ *                            c[0] = s
+ *     causal start, h >= N:  zn = z; iz = 1/z; z2n = z^(N-1), formed by N-2 successive
+ *                            multiplications by z starting from z (ours: no pow());
+ *                            s = c[0] + z2n*c[N-1]; z2n = z2n*(z2n*iz);
+ *                            for n = 1..N-2: { s = s + (zn+z2n)*c[n]; zn = zn*z; z2n = z2n*iz; }
+ *                            c[0] = s/(1 - zn*zn)
+ *     causal sweep:          for n = 1..N-1: c[n] = c[n] + z*c[n-1]
+ *     anticausal start:      c[N-1] = (z/(z*z-1)) * (z*c[N-2] + c[N-1])
+ *     anticausal sweep:      for n = N-2..0: c[n] = z*(c[n+1] - c[n])
+ * The multipliers and the divisor depend on (z, N) only and come from the host; the sequence of
+ * operations on the samples is the one above.
+ *
+ * Gather.  Per axis p, q, c and inside are exactly those of ife_resample; a voxel is inside when
+ * all three axes are.  The support of an inside index starts at
+ *   i0 = floor(c) - order/2 (odd orders),  floor(c + 0.5) - order/2 (even orders)
+ * (integer division), its taps are i0 .. i0+order, and with w = c - (double)(i0 + order/2) the
+ * weights are ITK's closed forms (left to right as written):
+ *   0: [1]        1: [1-w, w]
+ *   2: w1 = 0.75 - w*w; w2 = 0.5*(w - w1 + 1); w0 = 1 - w1 - w2
+ *   3: w3 = (1/6)*w*w*w; w0 = 1/6 + 0.5*w*(w-1) - w3; w2 = w + w0 - 2*w3; w1 = 1 - w0 - w2 - w3
+ *   4: w2_ = w*w; t = (1/6)*w2_; w0 = 0.5 - w; w0 = w0*w0; w0 = w0*((1/24)*w0);
+ *      t0 = w*(t - 11/24); t1 = 19/96 + w2_*(0.25 - t); w1 = t1 + t0; w3 = t1 - t0;
+ *      w4 = w0 + t0 + 0.5*w; w2 = 1 - w0 - w1 - w3 - w4
+ *   5: w2_ = w*w; w5 = (1/120)*w*w2_*w2_; w2_ = w2_ - w; w4_ = w2_*w2_; w = w - 0.5;
+ *      t = w2_*(w2_ - 3); w0 = (1/24)*(1/5 + w2_ + w4_) - w5;
+ *      t0 = (1/24)*(w2_*(w2_ - 5) + 46/5); t1 = (-1/12)*w*(t + 4); w2 = t0 + t1; w3 = t0 - t1;
+ *      t0 = (1/16)*(9/5 - t); t1 = (1/24)*w*(w4_ - w2_ - 5); w1 = t0 + t1; w4 = t0 - t1
+ * Tap indices are mirrored: P = 2n-2; i = |i| mod P; if (i >= n) i = P - i.  A source axis of
+ * length 1 is absent (ours): one tap, index 0, weight exactly 1.0, so that a volume with nz = 1
+ * behaves as a 2-D image.  The value is the nested sum x, then y, then z (ours; ITK's flat sum
+ * costs twice the multiplications), each sum starting from its first product:
+ *   r(j,k) = sum_i wx[i]*coef[..];  s(k) = sum_j wy[j]*r(j,k);  v = sum_k wz[k]*s(k)
+ * The float output rounds once; values beyond +-FLT_MAX clamp to +-FLT_MAX.
+ * Outside voxels: extrapolate = 0 gives default_value; extrapolate = 1 gives the SOURCE voxel (not
+ * the coefficient) at the clamped index per axis
+ *   e = (c >= n-1) ? n-1 : (c > 0 ? min(floor(c + 0.5), n-1) : 0)
+ * decided in double before any conversion (a NaN falls to 0).
+ * Non-finite source samples are legal and unspecified: they spread along their lines.
+ *
+ * ife_resample_bspline* build their coefficients in a workspace the context owns, 8 bytes per
+ * source voxel.  Refused as ife_resample refuses, before anything is written, and also with
+ * IFE_E_ARG: an order outside 0..5; an extrapolate outside {0, 1}.  coef may equal src in
+ * ife_bspline_coefficients_f64, which then runs in place; any other overlap is refused.
+ *
+ * ife_window_u8: scale = ((double)out_max - (double)out_min)/(window_max - window_min);
+ * shift = (double)out_min - window_min*scale; v < window_min gives out_min, v > window_max gives
+ * out_max, otherwise y = v*scale + shift, clamped to [0, 255], then truncated.  A NaN gives
+ * out_min (ours).  With a mask the result is mask[i] != 0 ? result : 0.  IFE_E_ARG:
+ * window_max <= window_min or either not finite; a null src or out; overlap of an input with the
+ * output.  IFE_E_SIZE: n <= 0.  One device, the context's stream. */
+int ife_bspline_coefficients(ife_ctx *ctx, const void *src, int src_dtype, const ife_volume_desc *vol,
+                             int order, double *coef, int mem);
+
+int ife_bspline_coefficients_f64(ife_ctx *ctx, const double *src, const ife_volume_desc *vol,
+                                 int order, double *coef, int mem);
+
+int ife_resample_bspline(ife_ctx *ctx, const void *src, int src_dtype, const ife_volume_desc *src_vol,
+                         const double src_origin[3], const ife_volume_desc *dst_vol,
+                         const double dst_origin[3], const double translation[3], int order,
+                         int extrapolate, double default_value, float *out, int mem);
+
+int ife_resample_bspline_f64(ife_ctx *ctx, const double *src, const ife_volume_desc *src_vol,
+                             const double src_origin[3], const ife_volume_desc *dst_vol,
+                             const double dst_origin[3], const double translation[3], int order,
+                             int extrapolate, double default_value, double *out, int mem);
+
+int ife_window_u8(ife_ctx *ctx, const double *src, const double *mask, int64_t n, double window_min,
+                  double window_max, uint8_t out_min, uint8_t out_max, uint8_t *out, int mem);
+
 /* ---- measurement ------------------------------------------------------------------- */
 
 #define IFE_MAX_KERNEL_KINDS 24
