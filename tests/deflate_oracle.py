@@ -113,7 +113,8 @@ def tokens(b, eq, lo, hi):
     return out
 
 
-def chunk_blocks(b, eq, lo, hi):
+def fixed_blocks(b, eq, lo, hi):
+    """Form F of chunk [lo, hi)."""
     w = _Bits()
     w.put(0, 1)   # BFINAL
     w.put(1, 2)   # BTYPE 01
@@ -122,7 +123,11 @@ def chunk_blocks(b, eq, lo, hi):
     w.put(*_EOB)
     w.put(0, 3)   # an empty stored block realigns
     w.align()
-    f = bytes(w.out) + b"\x00\x00\xff\xff"
+    return bytes(w.out) + b"\x00\x00\xff\xff"
+
+
+def chunk_blocks(b, eq, lo, hi):
+    f = fixed_blocks(b, eq, lo, hi)
     n = hi - lo
     if 5 + n <= len(f):
         return b"\x00" + n.to_bytes(2, "little") + (n ^ 0xFFFF).to_bytes(2, "little") + bytes(b[lo:hi])
@@ -161,20 +166,123 @@ def planted_run(L, at, seed=0):
     beginning at `at`.  Chunk 0 is zero up to C - 3000 and chunk 1 from C + 3000 on, but for the
     surroundings of the run and one stretch with all 256 byte values, so form F wins in both and
     every literal code occurs."""
-    rng = np.random.default_rng(1000 * L + at + seed)
+    return planted_runs(L, (at,), seed)
+
+
+def planted_runs(L, ats, seed=0):
+    """planted_run with one run of exactly L bytes at every offset of `ats` (ascending, at least
+    600 bytes from the end of one run to the start of the next, none over the stretch of all byte
+    values): the same background, and every run is exactly [at, at + L)."""
+    ats = tuple(ats)
+    rng = np.random.default_rng(1000 * L + ats[0] + seed)
     b = rng.integers(0, 256, 2 * C + 64, dtype=np.uint8)
-    keep = b[max(0, at - 8):at + L + 8].copy()
+    for prev, at in zip(ats, ats[1:]):
+        assert at - (prev + L) >= 600, (L, prev, at)
+    for at in ats:
+        assert at >= 5 and at + L + 8 <= b.size and (at + L + 8 <= 4096 or at - 8 >= 4096 + 256), (L, at)
+    keep = [b[max(0, at - 8):at + L + 8].copy() for at in ats]
     b[:C - 3000] = 0
     b[C + 3000:2 * C] = 0
     b[4096:4096 + 256] = np.arange(256, dtype=np.uint8)
-    b[max(0, at - 8):at + L + 8] = keep
+    for at, k in zip(ats, keep):
+        b[max(0, at - 8):at + L + 8] = k
+    for at in ats:
+        for i in range(at, at + L):
+            b[i] = b[i - 4]
+        for i in (at - 1, at + L):  # the run is exactly [at, at + L)
+            if b[i] == b[i - 4]:
+                b[i] ^= 0x55
+        eq = b[at - 1:at + L + 1] == b[at - 5:at + L - 3]
+        assert not eq[0] and eq[1:-1].all() and not eq[-1]
+    return b.tobytes()
+
+
+# Thread t of a chunk's workgroup owns bytes [128t, 128t + 128), a wave 8192: where the device hands
+# the start and the end of a run from one thread, and one wave, to the next.
+SEAM_LENGTHS = (1, 2, 3, 4, 127, 128, 129, 257, 258, 259, 260, 261, 516, 519)
+SEAM_STARTS = (8191, 9472, 10753)          # 127, 0, 1 modulo 128; the first at a wave seam
+# Exclusive ends, 0, 127, 1 modulo 128.  The first and the last are at wave seams, where the last
+# block of the run begins in one wave and takes its length from a break in the next.
+SEAM_ENDS = (16384, 17791, 24577)
+
+
+def seam_offsets(L):
+    """Six starts of runs of L bytes in chunk 0: three begin and three end (exclusive) one byte
+    before, at and one byte behind a thread seam, at least one of each at a wave seam."""
+    ats = SEAM_STARTS + tuple(e - L for e in SEAM_ENDS)
+    assert sorted(a % 128 for a in ats[:3]) == [0, 1, 127]
+    assert sorted((a + L) % 128 for a in ats[3:]) == [0, 1, 127]
+    assert any(abs(a - 8192 * round(a / 8192)) <= 1 for a in ats[:3])
+    assert any(abs(a + L - 8192 * round((a + L) / 8192)) <= 1 for a in ats[3:])
+    assert ats[-1] + L + 8 < C - 3000  # all in chunk 0, inside its zeros
+    return ats
+
+
+def seam_cases():
+    """name -> bytes, one buffer per length of SEAM_LENGTHS with the six runs of seam_offsets."""
+    return {"seams_%d" % L: planted_runs(L, seam_offsets(L)) for L in SEAM_LENGTHS}
+
+
+def _no_eq_bytes(rng, n):
+    """n bytes under 144 (literals of 8 bits), none equal to the byte four before it."""
+    b = rng.integers(0, 144, n, dtype=np.uint8)
+    for i in range(4, n):
+        while b[i] == b[i - 4]:
+            b[i] = rng.integers(0, 144)
+    return b
+
+
+def _plant_exact(b, at, L):
+    """Makes [at, at + L) the only run of b, which had none; the bytes stay under 144."""
     for i in range(at, at + L):
         b[i] = b[i - 4]
-    for i in (at - 1, at + L):  # the run is exactly [at, at + L)
+    for i in range(at + L, b.size):  # a changed byte may equal the one four behind it
         if b[i] == b[i - 4]:
-            b[i] ^= 0x55
-    eq = b[at - 1:at + L + 1] == b[at - 5:at + L - 3]
-    assert not eq[0] and eq[1:-1].all() and not eq[-1]
+            b[i] = (b[i] + 1) % 144
+    eq = np.zeros(b.size, bool)
+    eq[4:] = b[4:] == b[:-4]
+    assert eq[at:at + L].all() and eq.sum() == L and b.max() < 144
+
+
+TIE_RUNS = (0, 3, 4)  # no run: S by one byte; a run of 3: the tie, S; a run of 4: F by one byte
+
+
+def tie_cases():
+    """name -> bytes.  For n in (1000, C) and a run of r in TIE_RUNS bytes: literals of 8 bits
+    only, so form F takes n + 6, n + 5 (as long as S) and n + 4 bytes.  The run begins on the last
+    byte of a thread (128k + 127).  tie_<C + 1000>_3 has the tie in chunk 0 and a stored chunk
+    behind it, which a wrong size of chunk 0 misplaces."""
+    cases = {}
+    for n, at, total in ((1000, 383, 1000), (C, 128 * 100 + 127, C), (C, 128 * 100 + 127, C + 1000)):
+        for r in TIE_RUNS:
+            if total != n and r != 3:
+                continue
+            b = _no_eq_bytes(np.random.default_rng(7000 + total + r), total)
+            if r:
+                _plant_exact(b, at, r)
+            eq = np.zeros(total, bool)
+            eq[4:] = b[4:] == b[:-4]
+            flen = len(fixed_blocks(b, eq, 0, n))
+            got = chunk_blocks(b, eq, 0, n)
+            assert flen == {0: n + 6, 3: n + 5, 4: n + 4}[r], (n, r, flen)
+            assert (got[0] == 0 and len(got) == n + 5) if r < 4 else (got[0] != 0 and len(got) == n + 4)
+            cases["tie_%d_%d" % (total, r)] = b.tobytes()
+    return cases
+
+
+def edge_counts(mis):
+    """The two lengths at which, for a source `mis` bytes behind a 16-byte boundary, thread 0's
+    bytes end with its eighth 16-byte granule and reach one byte into the ninth."""
+    assert 0 <= mis < 16
+    return (128 - mis, 129 - mis)
+
+
+def edge_case(n):
+    """n zero bytes with random non-zero bytes at fixed places, the last byte among them, so that
+    matches and literals both occur and a last byte that was not loaded shows."""
+    b = np.zeros(n, np.uint8)
+    at = [i for i in (0, 5, 6, 7, 40, 77, 78, n - 17, n - 2, n - 1) if 0 <= i < n]
+    b[at] = np.random.default_rng(n).integers(1, 256, len(at), dtype=np.uint8)
     return b.tobytes()
 
 
@@ -211,4 +319,8 @@ def small_cases():
             cases["run_%d_at_%d" % (L, at)] = planted_run(L, at)
     cases["masked_volume"] = masked_volume().tobytes()
     cases["crossing_runs"] = crossing_runs()
+    cases.update(tie_cases())
+    cases.update(seam_cases())
+    for n in sorted({n for mis in range(16) for n in edge_counts(mis)}):
+        cases["edge_%d" % n] = edge_case(n)
     return cases
