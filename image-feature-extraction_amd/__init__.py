@@ -61,6 +61,7 @@ EXPORTS = (
     "ife_sort_f32", "ife_equalized_edges_f32", "ife_equalized_edges_f64", "ife_dense_histogram_f32", "ife_roi_histograms", "ife_bag_image",
     "ife_dense_rois", "ife_dense_roi_histograms", "ife_bag_image_dense",
     "ife_bag_dense_stream_begin", "ife_bag_dense_stream_next", "ife_bag_dense_stream_end",
+    "ife_roi_labels", "ife_dense_roi_labels",
     "ife_samples_create", "ife_samples_destroy", "ife_samples_count", "ife_samples_clear",
     "ife_samples_add_features", "ife_samples_add_image", "ife_samples_sort",
     "ife_samples_equalized_edges", "ife_samples_read_column",
@@ -191,6 +192,9 @@ def load_library():
                                                C.POINTER(i64), i32]
     lib.ife_bag_dense_stream_next.argtypes = [vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
     lib.ife_bag_dense_stream_end.argtypes = [vp]
+    lib.ife_roi_labels.argtypes = [vp, vp, i32, vd, vp, i64, C.POINTER(i32), i32, i32, vp, i32]
+    lib.ife_dense_roi_labels.argtypes = [vp, vp, i32, vp, i32, vd, C.POINTER(i64), C.POINTER(i32), i32, i32, vp,
+                                         i64, C.POINTER(i64), i32]
     lib.ife_samples_create.argtypes = [vp, i32, C.POINTER(vp)]
     lib.ife_samples_destroy.argtypes = [vp]
     lib.ife_samples_destroy.restype = None
@@ -266,6 +270,22 @@ def _sigma_arg(sigmas):
 def _size_arg(size_xyz):
     sx, sy, sz = (int(v) for v in size_xyz)
     return (C.c_int64 * 3)(sx, sy, sz)
+
+
+def _labels_arg(labels):
+    """The label volume as a contiguous uint8 array (ExtractLabels reads unsigned char)."""
+    labels = np.ascontiguousarray(labels)
+    if labels.dtype != np.uint8:
+        raise TypeError("labels must be uint8")
+    if labels.ndim != 3:
+        raise ValueError("labels must be a (z, y, x) volume")
+    return labels
+
+
+def _ignore_arg(ignore):
+    """(int array or None, count) of the ignored labels; the library checks their range."""
+    ignore = [int(v) for v in ignore]
+    return ((C.c_int * len(ignore))(*ignore) if ignore else None), len(ignore)
 
 
 def _ptr_array(ptrs):
@@ -1013,6 +1033,39 @@ class Context:
             _size_arg(size), edges.ctypes.data, ne, counts.ctypes.data, counts.shape[0],
             C.byref(got), MEM_HOST))
         return counts[:got.value]
+
+    # ---- per-region label modes (ExtractLabels) ----------------------------------------
+    def roi_labels(self, labels, rois, ignore=(), dominant=-1):
+        """The mode of the uint8 label volume inside every box of rois (n, 6) {x, y, z, sx, sy,
+        sz}: (n,) uint8.  ignore: labels that do not vote; dominant: a label that wins wherever
+        it occurs (-1: none); ties go to the smallest label (include/ife_hip.h has the rule)."""
+        labels = _labels_arg(labels)
+        rois = np.ascontiguousarray(rois, np.int64).reshape(-1, 6)
+        ign, n_ign = _ignore_arg(ignore)
+        d = _desc(labels.shape, (1.0, 1.0, 1.0))
+        out = np.empty(rois.shape[0], np.uint8)
+        self._chk(self._lib.ife_roi_labels(self._h, labels.ctypes.data, U8, C.byref(d), rois.ctypes.data,
+                                           rois.shape[0], ign, n_ign, int(dominant), out.ctypes.data, MEM_HOST))
+        return out
+
+    def dense_roi_labels(self, labels, gen_mask, size, ignore=(), dominant=-1):
+        """ctx.roi_labels for the boxes of ctx.dense_rois(gen_mask, size), without the boxes: the
+        labels of a dense bag in the row order of the bag, (n_rois,) uint8."""
+        if gen_mask is None:
+            raise TypeError("a generating mask is required")
+        labels = _labels_arg(labels)
+        n = self._dense_count(gen_mask, size)
+        gen_mask, gdt, gptr = _mask_arg(gen_mask)
+        if gen_mask.shape != labels.shape:
+            raise ValueError("labels and gen_mask differ in shape")
+        ign, n_ign = _ignore_arg(ignore)
+        d = _desc(labels.shape, (1.0, 1.0, 1.0))
+        out = np.empty(max(n, 1), np.uint8)
+        got = C.c_int64()
+        self._chk(self._lib.ife_dense_roi_labels(
+            self._h, labels.ctypes.data, U8, gptr, gdt, C.byref(d), _size_arg(size), ign, n_ign, int(dominant),
+            out.ctypes.data, out.shape[0], C.byref(got), MEM_HOST))
+        return out[:got.value]
 
     def bag_image_dense_stream(self, image, mask, sigmas, size, edges, gen_mask=None,
                                spacing=(1.0, 1.0, 1.0), values="frequencies", block_mb=0):

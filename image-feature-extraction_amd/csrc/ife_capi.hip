@@ -25,6 +25,7 @@
 #include "distance_kernels.hpp"
 #include "dense_kernels.hpp"
 #include "dense_plan.hpp"
+#include "labels_kernels.hpp"
 #include "deflate_kernels.hpp"
 #include "resample_kernels.hpp"
 #include "bspline_kernels.hpp"
@@ -1609,4 +1610,5 @@ int ife_reset_kernel_times(ife_ctx *ctx) {
 #include "resample_capi.inc"
 #include "bspline_capi.inc"  // shares the resampling checks
 #include "dense_capi.inc"
+#include "labels_capi.inc"  // shares the dense centres, budget and x / y passes
 #include "multi_capi.inc"

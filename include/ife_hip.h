@@ -667,6 +667,50 @@ int ife_bag_dense_stream_next(ife_ctx *ctx, void *rows, int64_t capacity_rows, i
                               int64_t *n_rows);
 int ife_bag_dense_stream_end(ife_ctx *ctx);
 
+/* ---- per-region label modes (tools/ExtractLabels.cxx:164-212) ------------------------------- *
+ * The label of a region is the mode of a label volume (IFE_U8; anything else is IFE_E_ARG) inside
+ * its box, given a set G of ignored labels (ignore[0..n_ignore), a HOST array, each in 0..255,
+ * duplicates allowed, may be empty) and a dominant label d (`dominant`, < 0: none, > 255:
+ * IFE_E_ARG).  n(l) is the number of voxels of the box that carry label l, l in 0..255; every
+ * voxel counts, there is no counting mask.  c(l) = 0 if l is in G, else n(l).
+ *   1. If d >= 0 and (n(d) > 0 or d is in G), the label is d.  (The reference asks
+ *      counts.count(d) > 0 after it has inserted the ignored labels into its map, :189-198, so an
+ *      ignored dominant label always wins.)
+ *   2. Else, if max c > 0, the label is the smallest l with c(l) = max c.
+ *   3. Else the label is the smallest member of G (every voxel of the box then carries an ignored
+ *      label, and a box has at least one voxel, so G is not empty).
+ * Where the maximum is unique this is what the reference computes.  Where it ties the reference
+ * returns whichever key its std::unordered_map iterates first (:201-208), which depends on
+ * insertion order and bucket count and not on the counts: parity is unpinned at ties, and "the
+ * smallest label" is this library's definition.
+ *
+ * ife_roi_labels: rois holds n_rois boxes {x, y, z, sx, sy, sz} as in ife_roi_histograms,
+ * out[n_rois] receives the labels; labels, rois and out follow `mem`.  IFE_E_ARG when a box leaves
+ * the volume or has a size below 1, IFE_E_SIZE for a box of more than 2^32-1 voxels (in DEVICE mode
+ * the boxes are checked on the device before they are used, and either fault is IFE_E_ARG); out is
+ * not written then.  n_rois == 0 is IFE_OK with nothing written.  The call blocks in both memory
+ * modes. */
+int ife_roi_labels(ife_ctx *ctx, const void *labels, int labels_dtype, const ife_volume_desc *vol,
+                   const int64_t *rois, int64_t n_rois, const int *ignore, int n_ignore,
+                   int dominant, uint8_t *out, int mem);
+
+/* out[r] = the label ife_roi_labels gives for the box ife_dense_rois numbers r, without the boxes:
+ * the labels of a dense bag in the row order of the bag.  Centres, numbering, the zero-region
+ * case, the capacity rule (capacity in labels; IFE_E_SIZE with *n_rois set and nothing written)
+ * and the counter limits (sx <= 255, sx*sy <= 65535, sx*sy*sz <= 2^32-1) are those documented
+ * above ife_dense_rois and ife_dense_roi_histograms.  out == NULL: only *n_rois is written.
+ * gen_mask (IFE_U8 or IFE_U16) must not be NULL: there is no counting mask to fall back on.
+ * labels, gen_mask and out follow `mem`; *n_rois is a HOST scalar.  All 256 label values are
+ * served.  n(l) at every centre is a separable box sum (csrc/labels_kernels.hpp), so the work per
+ * region does not depend on the box; beside the scratch of the box passes (sized from
+ * IFE_OPT_DENSE_SCRATCH_MB or the free memory: 1 + 3 * labels-per-group bytes per voxel) the call
+ * keeps 4 bytes per region.  IFE_E_NOMEM when the scratch of one label (4 bytes per voxel) does
+ * not fit. */
+int ife_dense_roi_labels(ife_ctx *ctx, const void *labels, int labels_dtype, const void *gen_mask,
+                         int gen_mask_dtype, const ife_volume_desc *vol, const int64_t size[3],
+                         const int *ignore, int n_ignore, int dominant, uint8_t *out,
+                         int64_t capacity, int64_t *n_rois, int mem);
+
 /* The tool's `samples( scales.size() * numFeatures )` (:165-166): one growing column per
  * (scale, feature), kept in device memory.  Belongs to the context it was created on. */
 typedef struct ife_samples ife_samples;
