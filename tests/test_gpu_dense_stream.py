@@ -49,7 +49,7 @@ def device_edges(ctx, img, lab, sigmas, nbins):
                      for f in feats for c in range(8)])
 
 
-def make_case(ctx, synth, shape, size, seed, base=False):
+def make_case(ctx, synth, shape, size, seed, base=False, nbins=NBINS):
     nz, ny, nx = shape
     img = synth.volume_f32(shape, seed)
     lab = np.ones(shape, np.uint16)
@@ -62,7 +62,7 @@ def make_case(ctx, synth, shape, size, seed, base=False):
         lab[3:6, 4:8, 20:30] = 0
         gen[:, :, ::11] = 0                      # 60 of the 660 fitting centres of a plane
         gen[6] = 0                               # a centre plane without a centre
-    edges = device_edges(ctx, img, lab, SIGMAS, NBINS)
+    edges = device_edges(ctx, img, lab, SIGMAS, nbins)
     return dict(img=img, lab=lab, gen=gen, size=size, edges=edges)
 
 
@@ -293,7 +293,70 @@ def test_a_second_begin_without_end_starts_cleanly(ctx, ife, base):
     assert ife.load_library().ife_bag_dense_stream_end(ctx._h) == ife.E_STATE
 
 
-# ---- 5. the tool ---------------------------------------------------------------------------------------------
+# ---- 5. the transposition at every tile shape --------------------------------------------------------------
+# csrc/dense_capi.inc dense_stream_count: dense_freq_kernel stages 64 rows x `hists` whole histograms
+# in DENSE_FREQ_LDS_WORDS = 12288 words of LDS at a pitch of rows + 1, 32 rows where one histogram
+# does not fit beside 64 (nb * 65 > 12288, that is nb >= 190); the last group of histograms and
+# the last tile of rows are partial where nothing divides.
+# Not reached: the strided y grid.  It needs more than 65535 groups of histograms, that is more
+# than 8192 scales.
+FREQ_LDS_WORDS = 12288
+NCOL = 8 * len(SIGMAS)
+# bins: rows of a tile, histograms of a group, groups, histograms of the last group
+TILINGS = {30: (64, 6, 3, 4), 189: (64, 1, 16, 1), 190: (32, 1, 16, 1), 255: (32, 1, 16, 1)}
+
+
+def tiling(nb, ncol):
+    tr = 64 if nb * 65 <= FREQ_LDS_WORDS else 32
+    hists = max(1, min(ncol, FREQ_LDS_WORDS // (tr + 1) // nb))
+    groups = -(-ncol // hists)
+    return tr, hists, groups, ncol - (groups - 1) * hists
+
+
+@pytest.fixture(scope="module", params=sorted(TILINGS))
+def many_bins(request, ctx, synth):
+    """The base case with `nb` bins and the bag ife_bag_image_dense gives for it: once per bin count,
+    shared by the four streams, never written to."""
+    nb = request.param
+    case = make_case(ctx, synth, (14, 12, 70), (5, 3, 4), 501, base=True, nbins=nb)
+    assert case["edges"].shape == (NCOL, nb - 1)
+    case["nb"] = nb
+    case["counts"] = ctx.bag_image_dense(case["img"], case["lab"], SIGMAS, case["size"], case["edges"],
+                                         gen_mask=case["gen"])
+    assert case["counts"].shape == (6000, NCOL, nb)
+    for a in (case["img"], case["lab"], case["gen"], case["edges"], case["counts"]):
+        a.setflags(write=False)
+    return case
+
+
+@pytest.mark.parametrize("block_mb", [0, 1], ids=["one-block", "one-plane"])
+@pytest.mark.parametrize("values", ["counts", "frequencies"])
+def test_transposition_at_every_tile_shape(ctx, ife, many_bins, values, block_mb):
+    nb = many_bins["nb"]
+    tr, hists, groups, last = tiling(nb, NCOL)
+    assert (tr, hists, groups, last) == TILINGS[nb]
+    if nb == 30:
+        assert 0 < last < hists                          # a partial last group of histograms
+    if nb == 189:
+        assert tiling(nb + 1, NCOL)[0] == 32             # the last bin count with 64-row tiles
+    blocks = stream(ctx, ife, many_bins, values, 0, block_mb=block_mb)
+    rows = [len(r) for _, r in blocks]
+    if block_mb:                                         # the 600 rows of one plane are beyond 1 MiB already
+        assert 600 * NCOL * nb * 4 > 1 << 20
+        assert rows == [600] * 10
+    else:
+        assert rows == [6000]
+    assert all(n % tr != 0 for n in rows)                # the last tile of rows is partial
+    got = joined(blocks, 6000)
+    if values == "counts":
+        assert got.dtype == np.uint32 and np.array_equal(got, many_bins["counts"])
+    else:
+        empty = many_bins["counts"].sum(-1, dtype=np.int32) == 0
+        assert empty.any() and not empty.all()
+        assert_frequencies(got, many_bins["counts"])
+
+
+# ---- 6. the tool ---------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def built():
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "image-feature-extraction_amd", "csrc")])
