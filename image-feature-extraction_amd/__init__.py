@@ -73,6 +73,8 @@ EXPORTS = (
     "ife_resample", "ife_resample_f64",
     "ife_bspline_coefficients", "ife_bspline_coefficients_f64", "ife_resample_bspline",
     "ife_resample_bspline_f64", "ife_window_u8",
+    "ife_mask_bounding_box", "ife_extract_region", "ife_label_membership",
+    "ife_device_alloc", "ife_device_upload", "ife_device_free",
 )
 
 
@@ -228,6 +230,12 @@ def load_library():
     lib.ife_resample_bspline.argtypes = [vp, vp, i32, vd, d3, vd, d3, d3, i32, i32, C.c_double, vp, i32]
     lib.ife_resample_bspline_f64.argtypes = [vp, vp, vd, d3, vd, d3, d3, i32, i32, C.c_double, vp, i32]
     lib.ife_window_u8.argtypes = [vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_uint8, C.c_uint8, vp, i32]
+    lib.ife_mask_bounding_box.argtypes = [vp, vp, i32, vd, C.POINTER(i64), C.POINTER(i64), i32]
+    lib.ife_extract_region.argtypes = [vp, vp, i32, vd, C.POINTER(i64), i32, vp, vp, i32, i32]
+    lib.ife_label_membership.argtypes = [vp, vp, i32, i64, C.POINTER(i32), i32, i32, i32, vp, i32]
+    lib.ife_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
+    lib.ife_device_upload.argtypes = [vp, vp, vp, C.c_size_t]
+    lib.ife_device_free.argtypes = [vp, vp]
     _lib = lib
     return lib
 
@@ -286,6 +294,41 @@ def _ignore_arg(ignore):
     """(int array or None, count) of the ignored labels; the library checks their range."""
     ignore = [int(v) for v in ignore]
     return ((C.c_int * len(ignore))(*ignore) if ignore else None), len(ignore)
+
+
+_BOX_DT = {**_RESAMPLE_DT}   # what ife_mask_bounding_box reads
+
+
+def _region_arg(index_xyz, size_xyz, flip, elem_bytes, src_shape_zyx, has_pad):
+    """(region[6], flip bits) of ife_extract_region, with the refusals that need no device."""
+    ix, iy, iz = (int(v) for v in index_xyz)
+    sx, sy, sz = (int(v) for v in size_xyz)
+    if elem_bytes not in (1, 2, 4, 8):
+        raise TypeError("elements of 1, 2, 4 or 8 bytes are copied (got %d)" % elem_bytes)
+    if min(sx, sy, sz) < 1:
+        raise ValueError("the region's size must be at least 1 on every axis")
+    if isinstance(flip, (int, np.integer)) and not isinstance(flip, (bool, np.bool_)):
+        bits = int(flip)
+        if not 0 <= bits <= 7:
+            raise ValueError("flip must be 0 .. 7 (bit a flips axis a) or three booleans (x, y, z)")
+    else:
+        fx, fy, fz = (bool(v) for v in flip)
+        bits = int(fx) | int(fy) << 1 | int(fz) << 2
+    nz, ny, nx = (int(v) for v in src_shape_zyx)
+    inside = all(i >= 0 and i + s <= n for i, s, n in ((ix, sx, nx), (iy, sy, ny), (iz, sz, nz)))
+    if not inside and not has_pad:
+        raise ValueError("the region reaches outside the source: a pad_value is required")
+    return (C.c_int64 * 6)(ix, iy, iz, sx, sy, sz), bits
+
+
+def _include_arg(include, inside, outside, dtype):
+    """(int array or None, count) of a label set, with the range refusals of ife_label_membership."""
+    top = int(np.iinfo(dtype).max)
+    include = [int(v) for v in include]
+    for name, v in [("include", v) for v in include] + [("inside", int(inside)), ("outside", int(outside))]:
+        if not 0 <= v <= top:
+            raise ValueError("%s value %d is outside 0 .. %d" % (name, v, top))
+    return ((C.c_int * len(include))(*include) if include else None), len(include)
 
 
 def _ptr_array(ptrs):
@@ -1066,6 +1109,84 @@ class Context:
             self._h, labels.ctypes.data, U8, gptr, gdt, C.byref(d), _size_arg(size), ign, n_ign, int(dominant),
             out.ctypes.data, out.shape[0], C.byref(got), MEM_HOST))
         return out[:got.value]
+
+    # ---- regions: mask bounding box, crop / pad / flip, label sets --------------------------
+    def mask_bounding_box_device(self, ptr, dtype, shape_zyx):
+        """((x0, y0, z0), (sx, sy, sz), count) of the foreground of a device mask of dtype code
+        U8, U16, I16 or F32; an empty mask gives zeros."""
+        d = _desc(shape_zyx, (1.0, 1.0, 1.0))
+        box = (C.c_int64 * 6)()
+        count = C.c_int64()
+        self._chk(self._lib.ife_mask_bounding_box(self._h, C.c_void_p(ptr or 0), int(dtype), C.byref(d), box,
+                                                  C.byref(count), MEM_DEVICE))
+        return tuple(box[0:3]), tuple(box[3:6]), count.value
+
+    def mask_bounding_box(self, mask):
+        """The tightest box around the foreground of a (z, y, x) mask (uint8, uint16, int16: != 0;
+        float32: any bit pattern but +-0) and the number of foreground voxels:
+        ((x0, y0, z0), (sx, sy, sz), count); an empty mask gives zeros."""
+        mask = np.ascontiguousarray(mask)
+        if mask.dtype not in _BOX_DT:
+            raise TypeError("mask must be uint8, uint16, int16 or float32")
+        if mask.ndim != 3:
+            raise ValueError("mask must be a (z, y, x) volume")
+        d = _desc(mask.shape, (1.0, 1.0, 1.0))
+        box = (C.c_int64 * 6)()
+        count = C.c_int64()
+        self._chk(self._lib.ife_mask_bounding_box(self._h, mask.ctypes.data, _BOX_DT[mask.dtype], C.byref(d), box,
+                                                  C.byref(count), MEM_HOST))
+        return tuple(box[0:3]), tuple(box[3:6]), count.value
+
+    def extract_region_device(self, src_ptr, elem_bytes, src_shape_zyx, index_xyz, size_xyz, dst_ptr,
+                              pad_value=None, flip=(False, False, False)):
+        """Enqueues on the context's stream and waits; src_ptr: the source, dst_ptr: size_xyz
+        elements of elem_bytes bytes, both in device memory.  pad_value: None or elem_bytes bytes."""
+        region, bits = _region_arg(index_xyz, size_xyz, flip, int(elem_bytes), src_shape_zyx, pad_value is not None)
+        pad = None if pad_value is None else bytes(pad_value)
+        if pad is not None and len(pad) != int(elem_bytes):
+            raise ValueError("pad_value must hold elem_bytes bytes")
+        d = _desc(src_shape_zyx, (1.0, 1.0, 1.0))
+        self._chk(self._lib.ife_extract_region(self._h, C.c_void_p(src_ptr or 0), int(elem_bytes), C.byref(d), region,
+                                               bits, pad, C.c_void_p(dst_ptr or 0), MEM_DEVICE, MEM_DEVICE))
+
+    def extract_region(self, src, index_xyz, size_xyz, pad_value=None, flip=(False, False, False)):
+        """The box of size_xyz at index_xyz of a (z, y, x) volume of any dtype of 1, 2, 4 or 8
+        bytes, as a new (sz, sy, sx) array of that dtype: a crop where the box is inside, a
+        constant pad (pad_value) where it reaches outside, mirrored along the axes of flip
+        (x, y, z).  Bits are copied, nothing is converted."""
+        src = np.ascontiguousarray(src)
+        if src.ndim != 3:
+            raise ValueError("src must be a (z, y, x) volume")
+        region, bits = _region_arg(index_xyz, size_xyz, flip, src.dtype.itemsize, src.shape, pad_value is not None)
+        pad = None if pad_value is None else np.array(pad_value, dtype=src.dtype).tobytes()
+        d = _desc(src.shape, (1.0, 1.0, 1.0))
+        out = np.empty((region[5], region[4], region[3]), src.dtype)
+        self._chk(self._lib.ife_extract_region(self._h, src.ctypes.data, src.dtype.itemsize, C.byref(d), region, bits,
+                                               pad, out.ctypes.data, MEM_HOST, MEM_HOST))
+        return out
+
+    def label_membership_device(self, labels_ptr, dtype, n, include, out_ptr, inside=1, outside=0):
+        """Enqueues on the context's stream and waits; labels_ptr and out_ptr: n elements of dtype
+        code U8 or U16 in device memory."""
+        if dtype not in (U8, U16):
+            raise TypeError("labels must be uint8 or uint16")
+        inc, n_inc = _include_arg(include, inside, outside, np.uint8 if dtype == U8 else np.uint16)
+        self._chk(self._lib.ife_label_membership(self._h, C.c_void_p(labels_ptr or 0), dtype, int(n), inc, n_inc,
+                                                 int(inside), int(outside), C.c_void_p(out_ptr or 0), MEM_DEVICE))
+
+    def label_membership(self, labels, include, inside=1, outside=0):
+        """`inside` where a uint8 or uint16 label occurs in `include`, `outside` elsewhere; the
+        result has the labels' shape and dtype.  include needs no order and may repeat values."""
+        labels = np.ascontiguousarray(labels)
+        if labels.dtype not in _MSK_DT:
+            raise TypeError("labels must be uint8 or uint16")
+        inc, n_inc = _include_arg(include, inside, outside, labels.dtype)
+        out = np.empty(labels.shape, labels.dtype)
+        if labels.size:
+            self._chk(self._lib.ife_label_membership(self._h, labels.ctypes.data, _MSK_DT[labels.dtype], labels.size,
+                                                     inc, n_inc, int(inside), int(outside), out.ctypes.data,
+                                                     MEM_HOST))
+        return out
 
     def bag_image_dense_stream(self, image, mask, sigmas, size, edges, gen_mask=None,
                                spacing=(1.0, 1.0, 1.0), values="frequencies", block_mb=0):

@@ -29,6 +29,7 @@
 #include "deflate_kernels.hpp"
 #include "resample_kernels.hpp"
 #include "bspline_kernels.hpp"
+#include "region_kernels.hpp"
 #define IFE_IIR_NS iir_exact
 #define IFE_IIR_FMA 0
 #include "iir_kernels.inc"
@@ -1611,4 +1612,5 @@ int ife_reset_kernel_times(ife_ctx *ctx) {
 #include "bspline_capi.inc"  // shares the resampling checks
 #include "dense_capi.inc"
 #include "labels_capi.inc"  // shares the dense centres, budget and x / y passes
+#include "region_capi.inc"
 #include "multi_capi.inc"

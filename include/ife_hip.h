@@ -927,6 +927,63 @@ int ife_resample_bspline_f64(ife_ctx *ctx, const double *src, const ife_volume_d
 int ife_window_u8(ife_ctx *ctx, const double *src, const double *mask, int64_t n, double window_min,
                   double window_max, uint8_t out_min, uint8_t out_max, uint8_t *out, int mem);
 
+/* ---- regions: mask bounding box, crop / pad / flip, label sets ------------------------------- *
+ *
+ * The preprocessing of tools/ExtractBoundingBox.cxx, ExtractMaskedRegion.cxx, ExtractSlices.cxx
+ * and PadImage.cxx.  Everything here moves or counts whole elements: there is no arithmetic on
+ * values, and results are exact.  One device, the context's stream; every call blocks.
+ *
+ * ife_mask_bounding_box: box = {x0, y0, z0, sx, sy, sz}, the tightest box around the foreground
+ * of `mask` (dense, x fastest), and *count, the number of foreground voxels.  box and count are
+ * HOST pointers whatever mem is.  mask_dtype: IFE_U8, IFE_U16, IFE_I16 or IFE_F32.  An integer
+ * element is foreground when it is != 0 (a uint16 of 256 is foreground); a float when its bit
+ * pattern is anything but +-0, (bits & 0x7fffffff) != 0, so that denormals and NaN are foreground
+ * whatever the denormal mode of a compare is.  An empty mask gives IFE_OK, six zeros and count 0.
+ * [ITK-upstream, parity unpinned] this is what ImageMaskSpatialObject<3>::
+ * GetAxisAlignedBoundingBoxRegion returns, and the union of the component boxes that
+ * ExtractSlices.cxx:123-155 builds.
+ *
+ * ife_extract_region: a copy of bits, no conversion; elem_bytes is 1, 2, 4 or 8.  region =
+ * {ix, iy, iz, sx, sy, sz} in the source's index space, sizes >= 1; the index may be negative and
+ * the box may reach beyond the source or lie wholly outside it.  dst is a dense volume of
+ * sx * sy * sz elements, x fastest, and
+ *   dst[x, y, z] = S(ix + fx(x), iy + fy(y), iz + fz(z))
+ *   fa(i) = size_a - 1 - i where bit a of flip (0 .. 7) is set, else i
+ *   S = the source inside [0, n) on every axis, elsewhere the elem_bytes bytes at the HOST pointer
+ *       pad_value.
+ * pad_value may be NULL only when the region lies inside the source.  This covers
+ * itk::ExtractImageFilter and RegionOfInterestImageFilter (region inside the source),
+ * ConstantPadImageFilter (index -lower, size n + lower + upper) and FlipImageFilter.  src_mem and
+ * dst_mem are independent, so that a volume uploaded once serves many fetches to the host.
+ * IFE_E_ARG: elem_bytes not 1, 2, 4 or 8; a size below 1; flip outside 0 .. 7; a NULL pad_value
+ * with a region that reaches outside; a null src, dst or region; a DEVICE pointer not aligned to
+ * elem_bytes; DEVICE src and dst ranges that overlap.  IFE_E_SIZE: a region of more than 2^40
+ * bytes, or a voxel count that overflows.
+ *
+ * ife_label_membership: out[i] = inside where labels[i] occurs in include[0 .. n_include), else
+ * outside (the functor of ExtractMaskedRegion.cxx:62-67).  labels_dtype is IFE_U8 or IFE_U16 and
+ * out has the same type.  include needs no order and may repeat values; n_include == 0 makes
+ * every element outside.  IFE_E_ARG: an include, inside or outside value outside the dtype's
+ * range; a null pointer; DEVICE labels and out that overlap.  IFE_E_SIZE: n <= 0 or n > 2^40. */
+int ife_mask_bounding_box(ife_ctx *ctx, const void *mask, int mask_dtype, const ife_volume_desc *vol,
+                          int64_t box[6], int64_t *count, int mem);
+
+int ife_extract_region(ife_ctx *ctx, const void *src, int elem_bytes, const ife_volume_desc *src_vol,
+                       const int64_t region[6], int flip, const void *pad_value, void *dst, int src_mem,
+                       int dst_mem);
+
+int ife_label_membership(ife_ctx *ctx, const void *labels, int labels_dtype, int64_t n, const int *include,
+                         int n_include, int inside, int outside, void *out, int mem);
+
+/* Device buffers for callers without a HIP runtime of their own (the host tools: ExtractSlices
+ * uploads its volume once and fetches every slice from it).  ife_device_alloc gives `bytes` bytes
+ * on the context's device, aligned to at least 256; ife_device_upload copies host bytes into such a
+ * buffer on the context's stream and waits; ife_device_free takes a pointer of ife_device_alloc
+ * (NULL is allowed) and waits for the stream first.  IFE_E_ARG: a null pointer, bytes == 0. */
+int ife_device_alloc(ife_ctx *ctx, size_t bytes, void **ptr);
+int ife_device_upload(ife_ctx *ctx, void *dst, const void *src, size_t bytes);
+int ife_device_free(ife_ctx *ctx, void *ptr);
+
 /* ---- measurement ------------------------------------------------------------------- */
 
 #define IFE_MAX_KERNEL_KINDS 24
