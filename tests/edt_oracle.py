@@ -9,6 +9,8 @@ algorithm under test: brute-force min-plus, no envelopes, no ballots.
 
 sq_dist(..., slabs=True) is the same arithmetic one slab at a time, for lines of a few hundred voxels;
 expected_distance_device_order sums the terms of ife_expected_distance in the device's order.
+ROW_PATTERNS / row_mask are the isolated-row masks that tests/test_gpu_distance.py runs and
+tests/test_distance_cpu.py classifies.
 
 Volumes are [z, y, x]; spacing is (sx, sy, sz)."""
 import numpy as np
@@ -94,6 +96,44 @@ def expected_distance_terms(mask, prob, spacing=(1.0, 1.0, 1.0), slabs=False, di
     if dist is None:
         dist = signed_distance_map(mask, spacing, slabs=slabs)
     return (dist[fg] * np.asarray(prob, np.float64)[fg])
+
+
+# ---- isolated rows: masks whose foreground lies in one row, so that every other row leaves the x
+# pass without a site and what the x pass writes in that row reaches every voxel ----------------
+SEGMENT = 64           # voxels per ballot of edt_x_kernel (csrc/distance_kernels.hpp)
+
+ROW_PATTERNS = {       # name: (nx, inclusive runs (first, last) of foreground along x)
+    "300_at0": (300, [(0, 0)]),
+    "300_at299": (300, [(299, 299)]),
+    "300_at63": (300, [(63, 63)]),
+    "300_at64": (300, [(64, 64)]),
+    "300_at10_290": (300, [(10, 10), (290, 290)]),
+    "300_run100_140": (300, [(100, 140)]),
+    "320_at63_256": (320, [(63, 63), (256, 256)]),
+    "320_at64_191": (320, [(64, 64), (191, 191)]),
+    "320_run60_200": (320, [(60, 200)]),
+    "65_at64": (65, [(64, 64)]),
+}
+ROW_ZY = (1, 2)        # the row of the foreground in the (3, 4, nx) form
+
+
+def row_mask(name, volume, dtype=np.uint8, value=1):
+    """(mask, (z, y) of its foreground row).  volume False: shape (1, 1, nx), where a run has sites
+    at its two ends only; True: shape (3, 4, nx) with the foreground in row z = 1, y = 2, where
+    every voxel of a run is a site."""
+    nx, runs = ROW_PATTERNS[name]
+    z, y = ROW_ZY if volume else (0, 0)
+    mask = np.zeros((3, 4, nx) if volume else (1, 1, nx), dtype)
+    for a, b in runs:
+        mask[z, y, a:b + 1] = value
+    return mask, (z, y)
+
+
+def segment_occupancy(site_row):
+    """Per 64-voxel segment of a row (the last one may be partial): does it hold a site?"""
+    site_row = np.asarray(site_row, bool)
+    pad = -site_row.size % SEGMENT
+    return np.concatenate([site_row, np.zeros(pad, bool)]).reshape(-1, SEGMENT).any(axis=1)
 
 
 REDUCE_THREADS = 256   # EDT_REDUCE_THREADS of csrc/distance_kernels.hpp

@@ -1,5 +1,6 @@
 """Signed distance map / expected distance, the part that needs no GPU: the numpy oracle agrees
-with itself (separable form against the definition) and with scipy, the two entry points are
+with itself (separable form against the definition) and with scipy, the isolated-row masks of
+tests/test_gpu_distance.py have the empty 64-voxel segments they are there for, the two entry points are
 declared, exported and bound, and the tool has the reference's command line and no CPU path."""
 import os
 import re
@@ -76,6 +77,84 @@ def test_oracle_contour_and_empty():
     box[:3, :3, :3] = True                        # touches three faces: sites only on the inner faces
     c = E.contour(box)
     assert not c[0, 0, 0] and c[2, 0, 0] and c[0, 2, 0] and c[0, 0, 2] and not c[1, 1, 1]
+
+
+def _row_case(name, volume):
+    """(sites of the foreground row, (z, y) of that row, shape); no other row holds a site."""
+    mask, (z, y) = E.row_mask(name, volume)
+    nx, runs = E.ROW_PATTERNS[name]
+    assert mask.shape == ((3, 4, nx) if volume else (1, 1, nx))
+    fg = np.zeros(nx, bool)
+    for a, b in runs:
+        assert 0 <= a <= b < nx
+        fg[a:b + 1] = True
+    assert np.array_equal(mask[z, y] != 0, fg) and np.count_nonzero(mask) == fg.sum()
+    site = E.contour(mask != 0)
+    assert site.sum() == site[z, y].sum() > 0
+    if volume:            # background above, below, before and behind: every voxel of a run
+        want = fg
+    else:                 # x neighbours only: the ends of a run that have a neighbour in the row
+        want = np.zeros(nx, bool)
+        for a, b in runs:
+            want[a] |= a > 0 or (a == b and b + 1 < nx)
+            want[b] |= b + 1 < nx or (a == b and a > 0)
+    assert np.array_equal(site[z, y], want), (name, volume)
+    return site[z, y], (z, y), mask.shape
+
+
+def test_isolated_rows_have_the_empty_segments_they_claim():
+    """edt_x_kernel needs a site from beyond a lane's own 64-voxel segment only where a segment of
+    the row is empty.  s_left[s] is parked before segment s is looked at and `next` is used before
+    it is updated, so the nearest segment always gets its value; a carry that is lost over an empty
+    segment shows from the second empty segment in a row on, or beyond an empty segment between
+    two occupied ones.  The set holds all of these, on both sides."""
+    before, after, between, before2, after2 = set(), set(), set(), set(), set()
+    for name in E.ROW_PATTERNS:
+        for volume in (False, True):
+            row, _, shape = _row_case(name, volume)
+            occ = E.segment_occupancy(row)
+            assert occ.size == (shape[2] + 63) // 64
+            k = np.flatnonzero(occ)
+            first, last = int(k[0]), int(k[-1])
+            case = (name, volume)
+            if first >= 1:
+                before.add(case)
+            if first >= 2:
+                before2.add(case)
+            if occ.size - 1 - last >= 1:
+                after.add(case)
+            if occ.size - 1 - last >= 2:
+                after2.add(case)
+            if not occ[first:last + 1].all():
+                between.add(case)
+    assert before and after and between and before2 and after2
+    # the claims of single patterns that the choice of the set rests on
+    assert ("300_at299", False) in before2 and ("300_at299", True) in before2
+    assert ("300_at0", False) in after2 and ("300_at64", True) in after2
+    assert {("300_at10_290", v) for v in (False, True)} | {("320_at63_256", v) for v in (False, True)} <= between
+    assert ("320_run60_200", False) in between       # sites at 60 and 200 only: segments 1 and 2 empty
+    assert ("320_run60_200", True) not in between    # every voxel a site: only the last segment is empty
+    assert ("65_at64", True) in before and ("65_at64", True) not in after   # a one-voxel last segment
+
+
+SINGLE_SITE = [n for n, (_, runs) in E.ROW_PATTERNS.items() if len(runs) == 1 and runs[0][0] == runs[0][1]]
+
+
+@pytest.mark.parametrize("spacing", [(1.0, 1.0, 1.0), (0.5, 2.0, 1.0), (0.7, 0.7, 2.5)])
+def test_oracle_single_site_rows_equal_the_closed_form(spacing):
+    """One site p: D2(v) = ((hx(p)-hx(x))^2 + (hy(p)-hy(y))^2) + (hz(p)-hz(z))^2 with h(i) =
+    float64(i) * spacing, the oracle's own operation order, so bit for bit at every spacing."""
+    assert sorted(SINGLE_SITE) == ["300_at0", "300_at299", "300_at63", "300_at64", "65_at64"]
+    for name in SINGLE_SITE:
+        for volume in (False, True):
+            row, (pz, py), shape = _row_case(name, volume)
+            px, = np.flatnonzero(row)
+            hx, hy, hz = (np.arange(n, dtype=np.float64) * np.float64(s) for n, s in zip(shape[::-1], spacing))
+            want = ((hx[px] - hx) ** 2)[None, None, :] + ((hy[py] - hy) ** 2)[None, :, None]
+            want = want + ((hz[pz] - hz) ** 2)[:, None, None]
+            site = np.zeros(shape, bool)
+            site[pz, py, px] = True
+            assert E.sq_dist(site, spacing).tobytes() == want.tobytes(), (name, volume)
 
 
 def test_oracle_against_scipy():

@@ -6,7 +6,13 @@ times a power of two, so nothing rounds and the map must equal the oracle bit fo
 candidate the envelope keeps.  Spacing (0.7, 0.7, 2.5): fl(s*i) carries one rounding, the
 difference of two such coordinates a relative error of at most 2n eps with n <= 130 here, about
 6e-14 on D2 after the squares and sums; the bound 1e-12 leaves a factor of about 15 for an
-envelope that picks a near-tied parabola."""
+envelope that picks a near-tied parabola.  (n <= 150 on the solids: 7e-14.)
+
+Noise at densities of 0.3 and more puts a site into every 64-voxel segment of every row, and a
+sparse mask's neighbouring rows supply nearer sites through the y and z passes; what the x pass
+carries across empty segments is seen by the isolated rows and the row limit below, lattice ties
+and deep candidate stacks by the solids."""
+import ctypes as C
 import math
 import os
 import subprocess
@@ -55,6 +61,35 @@ def _box():
     return m
 
 
+def _solid(shape, inside):
+    """mask of inside(z, y, x) over the voxel indices"""
+    z, y, x = np.ogrid[:shape[0], :shape[1], :shape[2]]
+    return inside(z, y, x).astype(np.uint8)
+
+
+def _ball():
+    return _solid((48, 48, 48), lambda z, y, x: (z - 23.5) ** 2 + (y - 23.5) ** 2 + (x - 23.5) ** 2 <= 21.0 ** 2)
+
+
+def _ellipsoid():     # 150 along x: three segments of the x pass (lattice ties, deep stacks; no carry is read)
+    return _solid((24, 40, 150), lambda z, y, x: ((z - 11.3) / 10.2) ** 2 + ((y - 19.6) / 17.9) ** 2
+                  + ((x - 74.2) / 70.5) ** 2 <= 1.0)
+
+
+def _shell():
+    def inside(z, y, x):
+        r2 = (z - 19.5) ** 2 + (y - 21.5) ** 2 + (x - 34.5) ** 2
+        return (r2 >= 12.0 ** 2) & (r2 <= 18.0 ** 2)
+    return _solid((40, 44, 70), inside)
+
+
+def _cone():          # the axis along z, the apex in the plane z = 0
+    return _solid((48, 48, 70), lambda z, y, x: np.sqrt((y - 23.5) ** 2 + (x - 34.5) ** 2) <= 0.45 * z)
+
+
+SOLIDS = {"ball": _ball, "ellipsoid_x150": _ellipsoid, "shell": _shell, "cone": _cone}
+SLABS = {"ellipsoid_x150", "cone"}     # the oracle's whole-volume temporary would be about 100 MB or more
+
 MASKS = {
     "x67": lambda: _random((3, 5, 67), 0.5, 1),
     "x130": lambda: _random((7, 9, 130), 0.5, 2),
@@ -69,6 +104,7 @@ MASKS = {
     "checkerboard": _checker,
     "box_on_three_faces": _box,
 }
+MASKS.update(SOLIDS)
 
 _d2 = {}
 
@@ -78,7 +114,7 @@ def oracle_d2(name, spacing):
     key = (name, spacing)
     if key not in _d2:
         m = MASKS[name]()
-        d2 = E.sq_dist(E.contour(m != 0), spacing)
+        d2 = E.sq_dist(E.contour(m != 0), spacing, slabs=name in SLABS)
         m.setflags(write=False)
         d2.setflags(write=False)
         _d2[key] = (m, d2)
@@ -113,6 +149,131 @@ def test_anisotropic_spacing(ctx, name):
         rel = float(np.max(err / np.maximum(np.abs(want), np.finfo(np.float64).tiny)))
         print("%s squared=%s: max |gpu - oracle| / |oracle| = %.3g" % (name, squared, rel))
         assert (err <= 1e-12 * np.abs(want)).all(), rel
+
+
+FINE = (0.1, 0.1, 0.1)
+
+
+@pytest.mark.parametrize("name", sorted(SOLIDS) + ["yz_d0.3"])
+def test_inexact_isotropic_spacing(ctx, name):
+    """Spacing 0.1 is no binary fraction, so every lattice tie of the unit grid (the rule on a
+    smooth solid) becomes a near tie that the roundings inside edt_remove decide.  Lines of at most
+    150 voxels: the module's derivation gives about 7e-14 on D2, the bound is the same 1e-12."""
+    mask, d2 = oracle_d2(name, FINE)
+    assert max(mask.shape) <= 150
+    for positive, squared in ((True, False), (False, True)):
+        got = ctx.signed_distance_map(mask, FINE, inside_is_positive=positive, squared=squared)
+        want = signed(mask, d2, positive, squared)
+        err = np.abs(got - want)
+        rel = float(np.max(err / np.maximum(np.abs(want), np.finfo(np.float64).tiny)))
+        print("%s squared=%s: max |gpu - oracle| / |oracle| = %.3g" % (name, squared, rel))
+        assert (err <= 1e-12 * np.abs(want)).all(), rel
+
+
+# ---- isolated rows: the foreground in one row, so that the x pass alone decides every voxel ------
+# (edt_oracle.ROW_PATTERNS; tests/test_distance_cpu.py shows which empty segments each row has)
+def assert_map_equals(ctx, mask, spacing, d2, what):
+    """Both signs, squared and not, bit for bit."""
+    for positive in (True, False):
+        for squared in (False, True):
+            got = ctx.signed_distance_map(mask, spacing, inside_is_positive=positive, squared=squared)
+            want = signed(mask, d2, positive, squared)
+            bad = np.flatnonzero(got.ravel() != want.ravel())
+            assert bad.size == 0, "%s positive=%s squared=%s: %d voxels differ, first %d: %r != %r" % (
+                what, positive, squared, bad.size, bad[0], got.ravel()[bad[0]], want.ravel()[bad[0]])
+
+
+@pytest.mark.parametrize("spacing", EXACT_SPACINGS, ids=["unit", "pow2"])
+@pytest.mark.parametrize("volume", [False, True], ids=["1x1", "3x4"])
+@pytest.mark.parametrize("name", sorted(E.ROW_PATTERNS))
+def test_isolated_row_bit_for_bit(ctx, name, volume, spacing):
+    mask, _ = E.row_mask(name, volume)
+    d2 = E.sq_dist(E.contour(mask != 0), spacing)
+    assert d2.max() < E.DBL_MAX
+    assert_map_equals(ctx, mask, spacing, d2, name)
+
+
+@pytest.mark.parametrize("volume", [False, True], ids=["1x1", "3x4"])
+def test_isolated_row_uint16_value_300(ctx, volume):
+    mask, _ = E.row_mask("320_at63_256", volume, np.uint16, 300)
+    assert mask.dtype == np.uint16 and mask.max() == 300
+    for spacing in EXACT_SPACINGS:
+        assert_map_equals(ctx, mask, spacing, E.sq_dist(E.contour(mask != 0), spacing), spacing)
+
+
+@pytest.mark.parametrize("volume", [False, True], ids=["1x1", "3x4"])
+def test_isolated_row_anisotropic(ctx, volume):
+    """One pattern, two sites with empty segments between them, so that both carries are read.
+    The module's derivation with n <= 300: about 1.3e-13 on D2, a factor of 7 inside the bound."""
+    name = "300_at10_290"
+    mask, _ = E.row_mask(name, volume)
+    d2 = E.sq_dist(E.contour(mask != 0), ANISO)
+    for positive, squared in ((True, False), (False, True)):
+        got = ctx.signed_distance_map(mask, ANISO, inside_is_positive=positive, squared=squared)
+        want = signed(mask, d2, positive, squared)
+        err = np.abs(got - want)
+        rel = float(np.max(err / np.maximum(np.abs(want), np.finfo(np.float64).tiny)))
+        print("%s squared=%s: max |gpu - oracle| / |oracle| = %.3g" % (name, squared, rel))
+        assert (err <= 1e-12 * np.abs(want)).all(), rel
+
+
+# ---- the row limit: EDT_MAX_NX = 64 * EDT_MAX_SEGS = 32768 (csrc/distance_kernels.hpp), where
+# s_bits and s_left of edt_x_kernel are exactly full ------------------------------------------------
+ROW_LIMIT = 32768
+assert ROW_LIMIT == 64 * 512
+
+
+@pytest.mark.parametrize("spacing", EXACT_SPACINGS, ids=["unit", "pow2"])
+@pytest.mark.parametrize("x", [0, ROW_LIMIT - 1], ids=["first", "last"])
+def test_row_limit_one_voxel_at_an_end(ctx, x, spacing):
+    """One site at one end, so that every other voxel takes it across up to 511 empty segments;
+    the two ends in separate calls, since a second site would serve the lanes a lost carry leaves
+    without one.  Every value is an integer times a power of two and at most 32767^2 * 4: exact."""
+    mask = np.zeros((1, 1, ROW_LIMIT), np.uint8)
+    mask[0, 0, x] = 1
+    site = E.contour(mask != 0)
+    assert site.sum() == 1 and site[0, 0, x]
+    d2 = E.sq_dist_allpairs(site, spacing)
+    assert d2.max() == ((ROW_LIMIT - 1) * spacing[0]) ** 2
+    assert_map_equals(ctx, mask, spacing, d2, "x = %d" % x)
+
+
+@pytest.mark.parametrize("spacing", EXACT_SPACINGS, ids=["unit", "pow2"])
+def test_row_limit_uint16_volume(ctx, spacing):
+    mask = np.zeros((2, 3, ROW_LIMIT), np.uint16)
+    mask[1, 0, 12345] = 300
+    site = E.contour(mask != 0)
+    assert site.sum() == 1 and site[1, 0, 12345]
+    assert_map_equals(ctx, mask, spacing, E.sq_dist_allpairs(site, spacing), "x = 12345")
+
+
+def test_one_voxel_beyond_the_row_limit_is_refused(ife, ctx):
+    lib = ife.load_library()
+    shape = (1, 1, ROW_LIMIT + 1)
+    mask = np.ones(shape, np.uint8)
+    mask[0, 0, 5] = 0
+    prob = np.ones(shape)
+    d = ife._desc(shape, (1.0, 1.0, 1.0))
+    out = np.full(shape, -77.25)
+    rc = lib.ife_signed_distance_map(ctx._h, mask.ctypes.data, ife.U8, C.byref(d), 1, 0, out.ctypes.data,
+                                     ife.MEM_HOST)
+    assert rc == ife.E_SIZE and b"32768" in lib.ife_last_error(ctx._h)
+    assert (out == -77.25).all()
+    value, n = C.c_double(-77.25), C.c_int64(-77)
+    rc = lib.ife_expected_distance(ctx._h, mask.ctypes.data, ife.U8, prob.ctypes.data, C.byref(d), C.byref(value),
+                                   C.byref(n), ife.MEM_HOST)
+    assert rc == ife.E_SIZE and b"32768" in lib.ife_last_error(ctx._h)
+    assert value.value == -77.25 and n.value == -77
+    with pytest.raises(ife.IfeError) as e:
+        ctx.signed_distance_map(mask)
+    assert e.value.code == ife.E_SIZE and "32768" in str(e.value)
+    with pytest.raises(ife.IfeError) as e:
+        ctx.expected_distance(mask, prob)
+    assert e.value.code == ife.E_SIZE and "32768" in str(e.value)
+    small = np.zeros((1, 1, 70), np.uint8)                         # the context is still usable
+    small[0, 0, 3] = 1
+    want = signed(small, E.sq_dist_allpairs(small != 0), True, True)
+    assert np.array_equal(ctx.signed_distance_map(small, squared=True), want)
 
 
 @pytest.mark.parametrize("fill,sign", [(0, -1.0), (1, 1.0)], ids=["all_zeros", "all_ones"])
@@ -208,6 +369,25 @@ def test_expected_distance(ctx, dtype):
     assert got_n == n == again_n
     assert abs(got - want) <= 2 * n * 2.0 ** -53 * want
     assert np.float64(got).tobytes() == np.float64(again).tobytes()
+
+
+def test_expected_distance_on_a_solid(ctx):
+    """The ellipsoid (rows with empty segments, deep stacks) through the reducing form of the last
+    pass: the bits of the documented summation order, and the bound against the exact sum."""
+    mask, d2 = oracle_d2("ellipsoid_x150", (1.0, 1.0, 1.0))
+    prob = np.random.default_rng(24).random(mask.shape)
+    dist = signed(mask, d2, True, False)
+    terms = E.expected_distance_terms(mask, prob, dist=dist)
+    n = int(np.count_nonzero(mask))
+    assert terms.size == n and (terms >= 0).all() and terms.max() > 0
+    want = math.fsum(terms) / n
+    replica, replica_n = E.expected_distance_device_order(mask, prob, dist=dist)
+    got, got_n = ctx.expected_distance(mask, prob)
+    print("expected distance: gpu %.17g oracle %.17g replica %.17g rel %.3g (bound %.3g)" % (
+        got, want, replica, abs(got - want) / want, 2 * n * 2.0 ** -53))
+    assert got_n == n == replica_n
+    assert abs(got - want) <= 2 * n * 2.0 ** -53 * want
+    assert np.float64(got).tobytes() == np.float64(replica).tobytes()
 
 
 def test_expected_distance_empty_mask(ctx):

@@ -202,6 +202,69 @@ def test_expected_distance_many_lines(ctx):
     assert np.float64(got).tobytes() == np.float64(replica).tobytes()
 
 
+# csrc/distance_capi.inc edt_run: edt_x_kernel runs min(ny * nz, 1 << 20) workgroups of one wave,
+# a row each; with more rows a workgroup takes a second one and overwrites its ballots in LDS.
+EDT_X_SHAPE = (1025, 1024, 1)
+assert 1025 * 1024 == 1049600 > 1 << 20          # rows of the x pass: ny * nz, of one voxel each
+EDT_X_SITES = [    # (z, y): isolated voxels, each a site; row = z * ny + y
+    [(0, 0), (3, 1000), (511, 77), (512, 512), (700, 1023), (1023, 1023), (1024, 0), (1024, 600), (1024, 1023)],
+    [(0, 0), (1, 1), (200, 900), (640, 3), (900, 450), (1023, 0), (1024, 1), (1024, 333), (1024, 1022),
+     (1022, 700)],
+]
+
+
+@pytest.fixture(scope="module")
+def edt_x_context(ife):
+    with ife.Context(0) as c:
+        yield c
+
+
+def test_distance_map_second_trip_of_the_x_kernel(edt_x_context):
+    """Two site sets back to back on one context: rows that a missing second trip leaves unwritten
+    cannot pass on what the call before left in the buffers.  The very first call sees a fresh
+    allocation, so it is the later ones (the unsquared map of the same sites, whose values differ
+    from the squared ones, and the second site set) that hold the second trip."""
+    nz, ny, nx = EDT_X_SHAPE
+    assert ny * nz > 1 << 20
+    for sites in EDT_X_SITES:
+        assert 8 <= len(sites) <= 12 and (0, 0) in sites
+        assert sum(z * ny + y >= 1 << 20 for z, y in sites) >= 2
+        mask = np.zeros(EDT_X_SHAPE, np.uint8)
+        for z, y in sites:
+            mask[z, y, 0] = 1
+        site = E.contour(mask != 0)
+        assert np.array_equal(site, mask != 0)
+        d2 = E.sq_dist_allpairs(site)
+        got = edt_x_context.signed_distance_map(mask, squared=True)
+        want = np.where(mask != 0, d2, -d2)
+        bad = np.flatnonzero(got.ravel() != want.ravel())
+        assert bad.size == 0, "%d voxels differ, first %d: %r != %r" % (
+            bad.size, bad[0], got.ravel()[bad[0]], want.ravel()[bad[0]])
+        got = edt_x_context.signed_distance_map(mask, inside_is_positive=False)
+        assert np.array_equal(got, np.where(mask != 0, -np.sqrt(d2), np.sqrt(d2)))
+
+
+def test_expected_distance_second_trip_of_the_x_kernel(edt_x_context):
+    """Small squares of foreground; two of them reach the plane z = 1024, the rows of the second
+    trip, where the ends of their edge are sites and the three voxels between are not (the face
+    of the volume makes no site), so terms of the sum come from distances written on that trip."""
+    nz, ny, nx = EDT_X_SHAPE
+    assert ny * nz > 1 << 20
+    mask = np.zeros(EDT_X_SHAPE, np.uint8)
+    for z, y, edge in [(0, 0, 5), (300, 500, 7), (800, 1017, 7), (1020, 40, 5), (1020, 700, 5)]:
+        mask[z:z + edge, y:y + edge, 0] = 2
+    site = E.contour(mask != 0)
+    assert mask[0].any() and site[1024].sum() == 4 and np.count_nonzero(mask[1024]) == 10
+    dist = np.sqrt(E.sq_dist_allpairs(site))
+    prob = np.random.default_rng(43).random(EDT_X_SHAPE)
+    n = int(np.count_nonzero(mask))
+    replica, replica_n = E.expected_distance_device_order(mask, prob, dist=dist)
+    assert replica > 0
+    got, got_n = edt_x_context.expected_distance(mask, prob)
+    assert got_n == n == replica_n
+    assert np.float64(got).tobytes() == np.float64(replica).tobytes()
+
+
 # ---- 4. sample columns over many chunks --------------------------------------------------------------
 # csrc/stats_kernels.hpp GATHER_CHUNK = 4096 voxels per workgroup of count_foreground_kernel and
 # gather_foreground_kernel; scan_chunks_kernel: 256 threads, ceil(nchunks / 256) chunks each.
