@@ -89,6 +89,7 @@ def test_edges_random_against_oracle_and_compiled_reference(ctx, ife, oracle):
     rng = np.random.default_rng(5)
     ref = oracle.ref_lib()
     ok = walked = 0
+    kinds = {1: 0, 3: 0}
     for _ in range(300):
         n = int(rng.integers(1, 3000))
         nb = int(rng.integers(1, 80))
@@ -101,6 +102,7 @@ def test_edges_random_against_oracle_and_compiled_reference(ctx, ife, oracle):
                 ctx.equalized_edges(v, nb)
             assert ei.value.code == (ife.E_ARG if e.rc == 1 else ife.E_STATE)
             walked += 1
+            kinds[e.rc] += 1
             continue
         got = ctx.equalized_edges(v, nb)
         assert np.array_equal(got, want)
@@ -108,6 +110,7 @@ def test_edges_random_against_oracle_and_compiled_reference(ctx, ife, oracle):
             assert np.array_equal(got, oracle.ref_equalized_edges(v, nb))
         ok += 1
     assert ok > 150
+    assert kinds[1] > 0 and kinds[3] > 0 and kinds[1] + kinds[3] == walked, kinds   # both error kinds occurred
 
 
 def test_dense_histogram(ctx, oracle):
