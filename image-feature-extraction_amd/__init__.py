@@ -75,6 +75,7 @@ EXPORTS = (
     "ife_resample_bspline_f64", "ife_window_u8",
     "ife_mask_bounding_box", "ife_extract_region", "ife_label_membership",
     "ife_device_alloc", "ife_device_upload", "ife_device_free",
+    "ife_sample_positions", "ife_random_rois", "ife_extract_rois",
 )
 
 
@@ -236,6 +237,11 @@ def load_library():
     lib.ife_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.ife_device_upload.argtypes = [vp, vp, vp, C.c_size_t]
     lib.ife_device_free.argtypes = [vp, vp]
+    draw = [vp, vp, i32, vd, C.POINTER(i32), i32, i32, C.POINTER(i64), C.c_uint64, C.c_uint32, C.c_uint64, i64, vp,
+            C.POINTER(i64), i32]
+    lib.ife_sample_positions.argtypes = draw
+    lib.ife_random_rois.argtypes = draw
+    lib.ife_extract_rois.argtypes = [vp, vp, i32, vd, vp, i64, vp, i32]
     _lib = lib
     return lib
 
@@ -329,6 +335,43 @@ def _include_arg(include, inside, outside, dtype):
         if not 0 <= v <= top:
             raise ValueError("%s value %d is outside 0 .. %d" % (name, v, top))
     return ((C.c_int * len(include))(*include) if include else None), len(include)
+
+
+def _draw_args(values, per_value, size_xyz, seed, stream, first_draw, n_draws, dtype):
+    """The scalar arguments of ife_sample_positions / ife_random_rois from values to n_draws, and
+    the number of sets, with the refusals that need no device."""
+    top = 255 if dtype == U8 else 65535
+    values = [int(v) for v in values]
+    if len(values) > 32:
+        raise ValueError("at most 32 values (got %d)" % len(values))
+    for v in values:
+        if not 0 <= v <= top:
+            raise ValueError("value %d is outside 0 .. %d" % (v, top))
+    if per_value and not values:
+        raise ValueError("per_value needs at least one value")
+    size = _size_arg(size_xyz)
+    if min(size) < 1:
+        raise ValueError("the box size must be at least 1 along every axis")
+    if int(n_draws) < 0:
+        raise ValueError("negative count")
+    for name, v, bits in (("seed", seed, 64), ("stream", stream, 32), ("first_draw", first_draw, 64)):
+        if not 0 <= int(v) < 1 << bits:
+            raise ValueError("%s must be an unsigned %d-bit number" % (name, bits))
+    arr = (C.c_int * len(values))(*values) if values else None
+    return (arr, len(values), 1 if per_value else 0, size, int(seed), int(stream), int(first_draw),
+            int(n_draws)), (len(values) if per_value else 1)
+
+
+def _draw_host(ctx, name, width, mask, n_draws, size, values, per_value, seed, stream, first_draw):
+    """Context.sample_positions (width ()) and Context.random_rois (width (6,)) on host arrays."""
+    mask, mdt, mptr = _mask_arg(mask)
+    if mask is None or mask.ndim != 3:
+        raise ValueError("mask must be a (z, y, x) volume")
+    args, n_sets = _draw_args(values, per_value, size, seed, stream, first_draw, n_draws, mdt)
+    out = np.empty((n_sets, int(n_draws)) + width, np.int64)
+    counts = Context._draw(ctx, name, mptr, mdt, mask.shape, out.ctypes.data if out.size else None, MEM_HOST, args,
+                           n_sets)
+    return out, counts
 
 
 def _ptr_array(ptrs):
@@ -1186,6 +1229,88 @@ class Context:
             self._chk(self._lib.ife_label_membership(self._h, labels.ctypes.data, _MSK_DT[labels.dtype], labels.size,
                                                      inc, n_inc, int(inside), int(outside), out.ctypes.data,
                                                      MEM_HOST))
+        return out
+
+    # ---- sampling: seeded draws of mask voxels and boxes, a batched box gather --------------
+    def _draw(self, name, mask_ptr, dtype, shape_zyx, out_ptr, mem, args, n_sets):
+        """One of the two sampling calls; returns n_admissible (n_sets,) int64.  Where a set is
+        empty and draws were asked for, the IfeError carries the counts as .n_admissible."""
+        d = _desc(shape_zyx, (1.0, 1.0, 1.0))
+        counts = np.zeros(n_sets, np.int64)
+        try:
+            self._chk(getattr(self._lib, name)(self._h, C.c_void_p(mask_ptr or 0), int(dtype), C.byref(d), *args,
+                                               C.c_void_p(out_ptr or 0),
+                                               counts.ctypes.data_as(C.POINTER(C.c_int64)), mem))
+        except IfeError as e:
+            e.n_admissible = counts
+            raise
+        return counts
+
+    def sample_positions_device(self, mask_ptr, dtype, shape_zyx, out_ptr, n_draws, size=(1, 1, 1), values=(),
+                                per_value=False, seed=0, stream=0, first_draw=0):
+        """Enqueues on the context's stream and waits; mask_ptr: the mask of dtype code U8 or U16,
+        out_ptr: sets * n_draws int64, both in device memory.  Returns n_admissible."""
+        if dtype not in (U8, U16):
+            raise TypeError("mask must be uint8 or uint16")
+        args, n_sets = _draw_args(values, per_value, size, seed, stream, first_draw, n_draws, dtype)
+        return Context._draw(self, "ife_sample_positions", mask_ptr, dtype, shape_zyx, out_ptr, MEM_DEVICE, args, n_sets)
+
+    def random_rois_device(self, mask_ptr, dtype, shape_zyx, out_ptr, n_draws, size=(1, 1, 1), values=(),
+                           per_value=False, seed=0, stream=0, first_draw=0):
+        """sample_positions_device with boxes: out_ptr holds sets * n_draws * 6 int64."""
+        if dtype not in (U8, U16):
+            raise TypeError("mask must be uint8 or uint16")
+        args, n_sets = _draw_args(values, per_value, size, seed, stream, first_draw, n_draws, dtype)
+        return Context._draw(self, "ife_random_rois", mask_ptr, dtype, shape_zyx, out_ptr, MEM_DEVICE, args, n_sets)
+
+    def sample_positions(self, mask, n_draws, size=(1, 1, 1), values=(), per_value=False, seed=0, stream=0,
+                         first_draw=0):
+        """Seeded draws, with replacement, of voxels of a uint8 or uint16 (z, y, x) mask around
+        which a box of `size` (x, y, z) fits the volume: (positions (sets, n_draws) int64 linear
+        indices, n_admissible (sets,)).  values empty: one set, mask != 0; per_value False: one
+        set, mask in values; per_value True: one set per value, drawn from stream + its place.
+        Draw first_draw + i depends on (seed, stream, its number) and the mask alone
+        (include/ife_hip.h has the definition).  n_draws == 0 gives the counts alone."""
+        return _draw_host(self, "ife_sample_positions", (), mask, n_draws, size, values, per_value, seed, stream,
+                          first_draw)
+
+    def random_rois(self, mask, n_draws, size, values=(), per_value=False, seed=0, stream=0, first_draw=0):
+        """sample_positions as boxes: (rois (sets, n_draws, 6) int64 {x - sx // 2, y - sy // 2,
+        z - sz // 2, sx, sy, sz}, n_admissible (sets,))."""
+        return _draw_host(self, "ife_random_rois", (6,), mask, n_draws, size, values, per_value, seed, stream,
+                          first_draw)
+
+    def extract_rois_device(self, src_ptr, elem_bytes, src_shape_zyx, rois_ptr, n_rois, dst_ptr):
+        """Enqueues on the context's stream and waits; src_ptr: the volume, rois_ptr: n_rois * 6
+        int64, dst_ptr: n_rois boxes of elem_bytes bytes per element, all in device memory."""
+        if int(elem_bytes) not in (1, 2, 4, 8):
+            raise TypeError("elements of 1, 2, 4 or 8 bytes are copied (got %d)" % elem_bytes)
+        if int(n_rois) < 0:
+            raise ValueError("negative count")
+        d = _desc(src_shape_zyx, (1.0, 1.0, 1.0))
+        self._chk(self._lib.ife_extract_rois(self._h, C.c_void_p(src_ptr or 0), int(elem_bytes), C.byref(d),
+                                             C.c_void_p(rois_ptr or 0), int(n_rois), C.c_void_p(dst_ptr or 0),
+                                             MEM_DEVICE))
+
+    def extract_rois(self, src, rois):
+        """The boxes rois (n, 6) {x, y, z, sx, sy, sz}, all of one size and inside the (z, y, x)
+        volume src of any dtype of 1, 2, 4 or 8 bytes, as a new (n, sz, sy, sx) array of that
+        dtype.  Bits are copied, nothing is converted."""
+        src = np.ascontiguousarray(src)
+        if src.ndim != 3:
+            raise ValueError("src must be a (z, y, x) volume")
+        if src.dtype.itemsize not in (1, 2, 4, 8):
+            raise TypeError("elements of 1, 2, 4 or 8 bytes are copied (got %d)" % src.dtype.itemsize)
+        rois = np.ascontiguousarray(rois, np.int64).reshape(-1, 6)
+        if rois.shape[0] == 0:
+            return np.empty((0, 0, 0, 0), src.dtype)
+        sx, sy, sz = (int(v) for v in rois[0, 3:])
+        if min(sx, sy, sz) < 1:
+            raise ValueError("the region's size must be at least 1 on every axis")
+        out = np.empty((rois.shape[0], sz, sy, sx), src.dtype)
+        d = _desc(src.shape, (1.0, 1.0, 1.0))
+        self._chk(self._lib.ife_extract_rois(self._h, src.ctypes.data, src.dtype.itemsize, C.byref(d), rois.ctypes.data,
+                                             rois.shape[0], out.ctypes.data, MEM_HOST))
         return out
 
     def bag_image_dense_stream(self, image, mask, sigmas, size, edges, gen_mask=None,

@@ -30,6 +30,7 @@
 #include "resample_kernels.hpp"
 #include "bspline_kernels.hpp"
 #include "region_kernels.hpp"
+#include "sampling_kernels.hpp"
 #define IFE_IIR_NS iir_exact
 #define IFE_IIR_FMA 0
 #include "iir_kernels.inc"
@@ -1613,4 +1614,5 @@ int ife_reset_kernel_times(ife_ctx *ctx) {
 #include "dense_capi.inc"
 #include "labels_capi.inc"  // shares the dense centres, budget and x / y passes
 #include "region_capi.inc"
+#include "sampling_capi.inc"  // shares the dense geometry and the scans
 #include "multi_capi.inc"

@@ -13,7 +13,8 @@
 // sliding box sums); only the counts come back.  Frequencies are formed as
 // DenseHistogram::getFrequencies does (DenseHistogram.h:55-60).  The dense variant streams
 // (ife_bag_dense_stream_*): the device forms the frequencies too and delivers the bag in blocks of
-// rows that are written as they arrive.
+// rows that are written as they arrive.  With IFE_DEVICE_SAMPLING=1 the sampled regions are the
+// device's seeded draws (ife/ROI/DeviceSampling.h) instead of the host generator's.
 #ifndef IFE_HOST_BAGTOOL_H
 #define IFE_HOST_BAGTOOL_H
 
@@ -32,6 +33,7 @@
 #include "ife/IO/IO.h"
 #include "ife/IO/ROIReader.h"
 #include "ife/ROI/DenseROIGenerator.h"
+#include "ife/ROI/DeviceSampling.h"
 #include "ife/ROI/RegionOfInterestGenerator.h"
 #include "ife/Util/Path.h"
 
@@ -145,6 +147,8 @@ inline int bag_main(int argc, char *argv[], BagVariant variant, const char *tool
       }
       const MaskImageType *genMask = roiMaskPath.empty() ? mask : roiMask.GetPointer();
       if (dense) rois = itk::DenseROIGenerator<MaskImageType>(genMask).generate(roiSize);
+      else if (DeviceSamplingFromEnvironment())  // opt-in: the device's seeded draws, the mask is not walked here
+        rois = randomRegions<MaskImageType>(genMask, std::vector<int>(), false, roiSize, numROIs, SamplingSeed(), 0)[0];
       else rois = itk::RegionOfInterestGenerator<MaskImageType>(genMask).generate(numROIs, roiSize);
       const std::string roiOutPath(Path::join(outDirPath, prefix + ".ROIInfo"));
       std::ofstream out(roiOutPath.c_str());

@@ -13,6 +13,8 @@
 // (uniform over the volume, with replacement, kept when the label is a foreground value,
 // until -S positions are kept; a fresh draw per scale as the reference's random iterator
 // gives).  The reference seeds from std::random_device; IFE_SEED fixes the seed here.
+// With IFE_DEVICE_SAMPLING=1 the positions are the device's seeded draws instead
+// (ife_sample_positions, stream = image number * scales + scale) and the mask is not walked here.
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -26,6 +28,7 @@
 #include "ife/Filters/ImageToEmphysemaFeaturesFilter.h"
 #include "ife/Host/ImageIO.h"
 #include "ife/IO/IO.h"
+#include "ife/ROI/DeviceSampling.h"
 #include "ife/Statistics/DetermineEdgesForEqualizedHistogram.h"
 
 const std::string VERSION("0.1");
@@ -77,6 +80,10 @@ int main(int argc, char *argv[]) {
   std::mt19937_64 gen;
   if (const char *seed = std::getenv("IFE_SEED")) gen.seed(std::strtoull(seed, nullptr, 10));
   else gen.seed(std::random_device()());
+  // IFE_DEVICE_SAMPLING=1: the positions of -S come from ife_sample_positions instead
+  const bool deviceSampling = ife::host::DeviceSamplingFromEnvironment();
+  const uint64_t samplingSeed = deviceSampling ? ife::host::SamplingSeed() : 0;
+  size_t imageNumber = 0;
 
   ife::host::Engine &engine = ife::host::Engine::Instance();
   SamplesHandle samples;
@@ -110,7 +117,21 @@ int main(int argc, char *argv[]) {
       const MaskPixelType *labels = mask->GetBufferPointer();
 
       std::vector<int64_t> positions;  // scale-major, nSamples per scale
-      if (nSamples > 0) {
+      if (nSamples > 0 && deviceSampling) {
+        // opt-in: every scale of every image draws from a stream of its own on the device
+        const std::vector<int> accept(foregroundValues.begin(), foregroundValues.end());
+        try {
+          for (size_t i = 0; i < scales.size(); ++i) {
+            const std::vector<int64_t> p = ife::host::randomPositions(
+                mask, accept, nSamples, samplingSeed, (uint32_t)(imageNumber * scales.size() + i));
+            positions.insert(positions.end(), p.begin(), p.end());
+          }
+        } catch (itk::ExceptionObject &e) {  // no foreground voxel among them
+          std::cerr << "No foreground voxel in mask '" << imageMaskPair.second << "'" << std::endl
+                    << "ExceptionObject: " << e << std::endl;
+          return EXIT_FAILURE;
+        }
+      } else if (nSamples > 0) {
         bool any = false;
         for (int64_t v = 0; v < nvox && !any; ++v)
           for (unsigned int acceptV : foregroundValues) any = any || labels[v] == acceptV;
@@ -145,6 +166,7 @@ int main(int argc, char *argv[]) {
                   << "ExceptionObject: " << e << std::endl;
         return EXIT_FAILURE;
       }
+      ++imageNumber;
     }
     engine.check(ife_samples_equalized_edges(engine.ctx(), samples.s, (int)nBins, edges.data()),
                  "determineEdgesForEqualizedHistogram");

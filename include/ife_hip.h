@@ -984,6 +984,68 @@ int ife_device_alloc(ife_ctx *ctx, size_t bytes, void **ptr);
 int ife_device_upload(ife_ctx *ctx, void *dst, const void *src, size_t bytes);
 int ife_device_free(ife_ctx *ctx, void *ptr);
 
+/* ---- sampling: seeded draws of mask voxels and boxes, a batched box gather --------------------- *
+ *
+ * The random steps of tools/GenerateROIs.cxx, GenerateROIsManyRegions.cxx, MakeBag.cxx (through
+ * ROI/RegionOfInterestGenerator.hxx:22-62) and DetermineHistogramBinEdges_MultiScaleEigenvalue
+ * Features.cxx:112-133, without the mask on the host, and the gather of tools/SampleROIs.cxx:151-167.
+ * The reference seeds its generators from the clock, so there is nothing to be equal to: the draw
+ * is defined here, and the device is held equal to tests/sampling_oracle.py's restatement of it.
+ * Integers only; results are exact.  One device, the context's stream; every call blocks.
+ *
+ * Volume and mask.  The volume is dense, x fastest, with at most 2^32-1 voxels (IFE_E_SIZE beyond,
+ * as for the dense calls).  mask_dtype is IFE_U8 or IFE_U16.  size = {sx, sy, sz}, each >= 1; NULL
+ * means {1, 1, 1}.  h = size / 2 by integer division (an even size is off-centre, as in
+ * ROI/DenseROIGenerator.hxx:35-40).  Voxel (x, y, z) fits when the box [x - hx, x - hx + sx) x
+ * [y - hy, ...) x [z - hz, ...) lies inside the volume.
+ *
+ * Sets.  values is a HOST array of n_values entries, 0 <= n_values <= 32.
+ *   n_values == 0:  one set, mask != 0
+ *   per_value == 0: one set, mask in values[0 .. n_values)
+ *   per_value == 1: n_values sets, set j is mask == values[j]; a repeated value is a set of its own
+ * A_j: the voxels of set j that fit, in increasing linear index x + nx * (y + ny * z); N_j = |A_j|.
+ *
+ * Draw k of set j, k = first_draw + i for 0 <= i < n_draws, taken as an unsigned 64-bit number:
+ *   o = Philox4x32-10(counter = (k mod 2^32, k >> 32, (stream + j) mod 2^32, 0),
+ *                     key = (seed mod 2^32, seed >> 32))
+ *   u = o[0] + 2^32 * o[1]
+ *   r = floor(u * N_j / 2^64)          the high word of the 64 x 64 bit product
+ *   the result is A_j[r]
+ * Uniform over the admissible voxels, with replacement, as the reference's rejection loop is; the
+ * bias of the multiply-shift is below N_j / 2^64.  Philox4x32-10 is the published function
+ * (Salmon et al., SC11): multipliers 0xD2511F53 (on word 0) and 0xCD9E8D57 (on word 2), key
+ * increments 0x9E3779B9 and 0xBB67AE85 after each of the first nine rounds, a round
+ *   c <- (hi(M1 * c2) ^ c1 ^ k0, lo(M1 * c2), hi(M0 * c0) ^ c3 ^ k1, lo(M0 * c0)).
+ * Counter and key all zero give 6627e8d5 e169c58d bc57ac4c 9b00dbd8.  A draw depends on (seed,
+ * stream + j, k) and the mask alone: draws [0, 100) are draws [0, 40) followed by [40, 100).
+ *
+ * ife_sample_positions: positions[set][i] = the linear index of the draw.  ife_random_rois:
+ * rois[set][i] = {x - hx, y - hy, z - hz, sx, sy, sz} of the drawn voxel (x, y, z).  mask and the
+ * output follow mem; n_admissible is a HOST array of one entry per set and receives N_j.
+ * n_draws == 0 with a NULL output is legal and gives the counts alone.  Where some N_j == 0 and
+ * n_draws > 0 the call writes n_admissible, returns IFE_E_ARG with a message that names the set
+ * and writes nothing else (the reference would draw forever).  IFE_E_ARG also: a value outside the
+ * dtype's range, per_value with n_values == 0, n_values outside 0 .. 32, a size below 1, a
+ * negative count, a null pointer, a DEVICE pointer not aligned to its element size.  IFE_E_SIZE:
+ * more than 2^36 draws over all sets.
+ *
+ * ife_extract_rois: dst[r][z][y][x] = src[rois[r].z0 + z][rois[r].y0 + y][rois[r].x0 + x], a copy
+ * of bits of elements of 1, 2, 4 or 8 bytes; rois = [n_rois][6] as above; src, rois and dst follow
+ * mem.  All boxes must have the size of the first, at least 1, and lie inside the volume, else
+ * IFE_E_ARG with dst untouched; DEVICE boxes are checked on the device before anything reads
+ * through them.  n_rois == 0 is IFE_OK.  IFE_E_SIZE: more than 2^40 bytes of output. */
+int ife_sample_positions(ife_ctx *ctx, const void *mask, int mask_dtype, const ife_volume_desc *vol,
+                         const int *values, int n_values, int per_value, const int64_t *size, uint64_t seed,
+                         uint32_t stream, uint64_t first_draw, int64_t n_draws, int64_t *positions,
+                         int64_t *n_admissible, int mem);
+
+int ife_random_rois(ife_ctx *ctx, const void *mask, int mask_dtype, const ife_volume_desc *vol, const int *values,
+                    int n_values, int per_value, const int64_t *size, uint64_t seed, uint32_t stream,
+                    uint64_t first_draw, int64_t n_draws, int64_t *rois, int64_t *n_admissible, int mem);
+
+int ife_extract_rois(ife_ctx *ctx, const void *src, int elem_bytes, const ife_volume_desc *vol, const int64_t *rois,
+                     int64_t n_rois, void *dst, int mem);
+
 /* ---- measurement ------------------------------------------------------------------- */
 
 #define IFE_MAX_KERNEL_KINDS 24
