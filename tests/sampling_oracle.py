@@ -27,6 +27,28 @@ def rank(seed, stream, k, n):
     return ((o[0] + (o[1] << 32)) * n) >> 64
 
 
+def ranks(seed, stream, k_array, n):
+    """rank() of every draw number of k_array (non-negative integers, each taken mod 2^64) at once:
+    an int64 array of k_array's shape.  The ten rounds run on uint64 arrays of 32-bit words, whose
+    products with the 32-bit multipliers fit 64 bits; the final * n >> 64 is done in Python
+    integers, as in rank()."""
+    k = np.asarray(k_array)
+    if k.dtype != np.uint64:   # Python integers beyond 2^64 - 1 included
+        k = np.array([int(v) & ((1 << 64) - 1) for v in k.reshape(-1)], np.uint64).reshape(k.shape)
+    shape, k = k.shape, k.reshape(-1)
+    m32, s32 = np.uint64(MASK32), np.uint64(32)
+    c = [k & m32, k >> s32, np.full(k.shape, int(stream) & MASK32, np.uint64), np.zeros(k.shape, np.uint64)]
+    key = [int(seed) & MASK32, (int(seed) >> 32) & MASK32]
+    for rnd in range(10):
+        p0, p1 = np.uint64(M0) * c[0], np.uint64(M1) * c[2]
+        c = [(p1 >> s32) ^ c[1] ^ np.uint64(key[0]), p1 & m32, (p0 >> s32) ^ c[3] ^ np.uint64(key[1]), p0 & m32]
+        if rnd < 9:
+            key = [(key[0] + W0) & MASK32, (key[1] + W1) & MASK32]
+    u = c[0] + (c[1] << s32)
+    n = int(n)
+    return np.array([(int(v) * n) >> 64 for v in u], np.int64).reshape(shape)
+
+
 def fits(shape_zyx, size_xyz):
     """Boolean (z, y, x) volume: the box of size_xyz around the voxel lies inside the volume."""
     out = np.ones(shape_zyx, bool)
@@ -60,11 +82,13 @@ def sample_positions(mask, n_draws, size_xyz=(1, 1, 1), values=(), per_value=Fal
     sets = admissible(mask, size_xyz, values, per_value)
     counts = np.array([len(a) for a in sets], np.int64)
     out = np.empty((len(sets), n_draws), np.int64)
+    # the draw numbers modulo 2^64 (uint64 arrays wrap)
+    k = np.full(n_draws, int(first_draw) & ((1 << 64) - 1), np.uint64) + np.arange(n_draws, dtype=np.uint64)
     for j, a in enumerate(sets):
         if n_draws and len(a) == 0:
             raise ValueError("set %d is empty" % j)
-        for i in range(n_draws):
-            out[j, i] = a[rank(seed, stream + j, first_draw + i, len(a))]
+        if n_draws:
+            out[j] = a[ranks(seed, stream + j, k, len(a))]
     return out, counts
 
 

@@ -50,6 +50,36 @@ def test_counter_words():
     assert S.rank(seed, 3, k + 2 ** 64, 1000) == S.rank(seed, 3, k, 1000)
 
 
+@pytest.mark.parametrize("seed,stream,first", [
+    (12345, 0, 0),                                 # the draws of RANKS, and a few thousand more
+    (6, 9, 2 ** 32 - 3),                           # the draw number crosses into the second counter word
+    (6, 9, 2 ** 64 - 3),                           # and wraps at 2^64
+    ((0xDEADBEEF << 32) | 6, 2, 5),                # a seed with a high word
+    (6, 2 ** 32 - 1, 0), (6, 2 ** 32, 0),          # the last stream, and the one a second set wraps to
+])
+def test_ranks_equal_rank(seed, stream, first):
+    """The vectorised generator against the scalar one, which the known answers above pin."""
+    count = 3000 if first == 0 else 40
+    numbers = [first + i for i in range(count)]          # Python integers, beyond 2^64 - 1 too
+    for n in (1, 7, 1000, 2 ** 31 + 11, 2 ** 32 - 1):
+        want = [S.rank(seed, stream, k, n) for k in numbers]
+        got = S.ranks(seed, stream, numbers, n)
+        assert got.dtype == np.int64 and got.shape == (count,) and [int(v) for v in got] == want
+        wrapped = np.array([k % 2 ** 64 for k in numbers], np.uint64)    # and as a uint64 array
+        assert np.array_equal(S.ranks(seed, stream, wrapped, n), got)
+    assert np.array_equal(S.ranks(seed, stream, np.array(numbers[:12], object).reshape(3, 4), 1000),
+                          np.array([S.rank(seed, stream, k, 1000) for k in numbers[:12]]).reshape(3, 4))
+    assert S.ranks(seed, stream, [], 5).shape == (0,)
+
+
+def test_ranks_known_lists_and_the_high_seed_word():
+    for seed, stream, n, want in RANKS:
+        assert [int(v) for v in S.ranks(seed, stream, range(8), n)] == want
+    k = np.arange(64, dtype=np.uint64)
+    assert not np.array_equal(S.ranks((0xDEADBEEF << 32) | 6, 0, k, 1000), S.ranks(6, 0, k, 1000))
+    assert np.array_equal(S.ranks(6, 2 ** 32 + 3, k, 1000), S.ranks(6, 3, k, 1000))
+
+
 def _brute_fits(shape, size):
     nz, ny, nx = shape
     out = np.zeros(shape, bool)
