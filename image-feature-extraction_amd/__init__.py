@@ -76,6 +76,7 @@ EXPORTS = (
     "ife_mask_bounding_box", "ife_extract_region", "ife_label_membership",
     "ife_device_alloc", "ife_device_upload", "ife_device_free",
     "ife_sample_positions", "ife_random_rois", "ife_extract_rois",
+    "ife_value_census_f32", "ife_threshold_mask", "ife_roi_coverage",
 )
 
 
@@ -242,6 +243,10 @@ def load_library():
     lib.ife_sample_positions.argtypes = draw
     lib.ife_random_rois.argtypes = draw
     lib.ife_extract_rois.argtypes = [vp, vp, i32, vd, vp, i64, vp, i32]
+    lib.ife_value_census_f32.argtypes = [vp, vp, i64, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), i32]
+    lib.ife_threshold_mask.argtypes = [vp, vp, i64, C.c_float, C.c_float, vp, C.POINTER(i64), i32]
+    lib.ife_roi_coverage.argtypes = [vp, vp, i32, vd, vp, i64, C.POINTER(i64), i32, C.POINTER(i64), C.POINTER(i64),
+                                     C.POINTER(i64), i32]
     _lib = lib
     return lib
 
@@ -372,6 +377,30 @@ def _draw_host(ctx, name, width, mask, n_draws, size, values, per_value, seed, s
     counts = Context._draw(ctx, name, mptr, mdt, mask.shape, out.ctypes.data if out.size else None, MEM_HOST, args,
                            n_sets)
     return out, counts
+
+
+def _threshold_args(low, high):
+    """The bounds of ife_threshold_mask as the float32 values the library compares with, and the
+    refusals that need no device."""
+    low, high = np.float32(low), np.float32(high)
+    if np.isnan(low) or np.isnan(high):
+        raise ValueError("a threshold is not a number")
+    if low > high:
+        raise ValueError("Lower threshold cannot be greater than upper threshold.")
+    return C.c_float(float(low)), C.c_float(float(high))
+
+
+def _round_ends_arg(round_ends, n_rois):
+    """(int64 array, count) of the round ends of ife_roi_coverage, with the refusals that need no
+    device."""
+    ends = [int(v) for v in round_ends]
+    if not 1 <= len(ends) <= 64:
+        raise ValueError("between 1 and 64 round ends are required (got %d)" % len(ends))
+    if any(b < a for a, b in zip([0] + ends, ends)):
+        raise ValueError("round_ends must be non-negative and must not decrease")
+    if ends[-1] > int(n_rois):
+        raise ValueError("round end %d lies beyond the %d boxes" % (ends[-1], int(n_rois)))
+    return (C.c_int64 * len(ends))(*ends), len(ends)
 
 
 def _ptr_array(ptrs):
@@ -1312,6 +1341,110 @@ class Context:
         self._chk(self._lib.ife_extract_rois(self._h, src.ctypes.data, src.dtype.itemsize, C.byref(d), rois.ctypes.data,
                                              rois.shape[0], out.ctypes.data, MEM_HOST))
         return out
+
+    # ---- census and coverage: the two questions of ImageBrowser ------------------------------
+    def _census(self, values_ptr, n, uniq_ptr, counts_ptr, capacity, mem):
+        """One ife_value_census_f32 call; returns (n_unique, n_nan).  Where the outputs are too
+        small the IfeError carries the two counts as .n_unique and .n_nan."""
+        nu, nn = C.c_int64(-1), C.c_int64(-1)
+        try:
+            self._chk(self._lib.ife_value_census_f32(self._h, C.c_void_p(values_ptr or 0), int(n),
+                                                     C.c_void_p(uniq_ptr or 0), C.c_void_p(counts_ptr or 0),
+                                                     int(capacity), C.byref(nu), C.byref(nn), mem))
+        except IfeError as e:
+            e.n_unique, e.n_nan = nu.value, nn.value
+            raise
+        return nu.value, nn.value
+
+    def value_census_device(self, values_ptr, n, uniq_ptr=None, counts_ptr=None, capacity=0):
+        """Enqueues on the context's stream and waits; values_ptr: n float32, uniq_ptr: capacity
+        float32, counts_ptr: capacity uint32, all in device memory.  Returns (n_unique, n_nan);
+        capacity 0 without outputs gives the two counts alone."""
+        if int(n) <= 0:
+            raise ValueError("the element count must be positive")
+        if int(capacity) < 0:
+            raise ValueError("negative capacity")
+        return Context._census(self, values_ptr, n, uniq_ptr, counts_ptr, capacity, MEM_DEVICE)
+
+    def value_census(self, values):
+        """The distinct values of a float32 array in ascending order and how often each occurs:
+        (uniq float32, counts uint32, n_nan).  NaNs are left out and counted; -0 and +0 are one
+        value, reported as +0; any other two elements are one value iff their bits are equal.
+        Two library calls, the first for the sizes of the outputs: the array is uploaded and
+        sorted twice (value_census_device on a resident array saves the uploads, not the sorts)."""
+        values = np.ascontiguousarray(values)
+        if values.dtype != np.float32:
+            raise TypeError("values must be float32")
+        if values.size == 0:
+            raise ValueError("the element count must be positive")
+        n_unique, n_nan = Context._census(self, values.ctypes.data, values.size, None, None, 0, MEM_HOST)
+        uniq, counts = np.empty(n_unique, np.float32), np.empty(n_unique, np.uint32)
+        if n_unique:
+            Context._census(self, values.ctypes.data, values.size, uniq.ctypes.data, counts.ctypes.data, n_unique,
+                            MEM_HOST)
+        return uniq, counts, n_nan
+
+    def threshold_mask_device(self, image_ptr, n, low, high, mask_ptr):
+        """Enqueues on the context's stream and waits; image_ptr: n float32, mask_ptr: n bytes,
+        both in device memory.  Returns the number of ones."""
+        low, high = _threshold_args(low, high)
+        if int(n) <= 0:
+            raise ValueError("the element count must be positive")
+        count = C.c_int64()
+        self._chk(self._lib.ife_threshold_mask(self._h, C.c_void_p(image_ptr or 0), int(n), low, high,
+                                               C.c_void_p(mask_ptr or 0), C.byref(count), MEM_DEVICE))
+        return count.value
+
+    def threshold_mask(self, image, low, high):
+        """(mask uint8 of the image's shape, count): 1 where low <= image <= high, both ends
+        inclusive (itk::BinaryThresholdImageFilter), 0 elsewhere and at NaNs; -0 equals +0."""
+        image = np.ascontiguousarray(image)
+        if image.dtype != np.float32:
+            raise TypeError("image must be float32")
+        low, high = _threshold_args(low, high)
+        if image.size == 0:
+            raise ValueError("the element count must be positive")
+        mask = np.empty(image.shape, np.uint8)
+        count = C.c_int64()
+        self._chk(self._lib.ife_threshold_mask(self._h, image.ctypes.data, image.size, low, high, mask.ctypes.data,
+                                               C.byref(count), MEM_HOST))
+        return mask, count.value
+
+    def _coverage(self, mask_ptr, dtype, shape_zyx, rois_ptr, n_rois, round_ends, mem):
+        ends, n_rounds = _round_ends_arg(round_ends, n_rois)
+        d = _desc(shape_zyx, (1.0, 1.0, 1.0))
+        visited, hits = np.zeros(n_rounds, np.int64), np.zeros(n_rounds, np.int64)
+        region = C.c_int64()
+        p64 = C.POINTER(C.c_int64)
+        self._chk(self._lib.ife_roi_coverage(self._h, C.c_void_p(mask_ptr or 0), int(dtype), C.byref(d),
+                                             C.c_void_p(rois_ptr or 0), int(n_rois), ends, n_rounds,
+                                             visited.ctypes.data_as(p64), hits.ctypes.data_as(p64), C.byref(region),
+                                             mem))
+        return visited, hits, region.value
+
+    def roi_coverage_device(self, mask_ptr, dtype, shape_zyx, rois_ptr, n_rois, round_ends):
+        """Enqueues on the context's stream and waits; mask_ptr: the mask of dtype code U8 or U16,
+        rois_ptr: n_rois * 6 int64, both in device memory.  Returns (visited, hits, region_size)."""
+        if dtype not in (U8, U16):
+            raise TypeError("mask must be uint8 or uint16")
+        if int(n_rois) < 0:
+            raise ValueError("negative count")
+        return Context._coverage(self, mask_ptr, dtype, shape_zyx, rois_ptr, n_rois, round_ends, MEM_DEVICE)
+
+    def roi_coverage(self, mask, rois, round_ends):
+        """How much of a uint8 or uint16 (z, y, x) mask a growing list of boxes covers.  rois (n, 6)
+        {x, y, z, sx, sy, sz}, of any sizes; round r is the union of the boxes before
+        round_ends[r] (non-decreasing, at most n, at most 64 rounds).  Returns (visited (rounds,)
+        int64 voxels of the union, hits (rounds,) of them with mask != 0, region_size the number
+        of voxels with mask != 0)."""
+        mask, mdt, mptr = _mask_arg(mask)
+        if mask is None or mask.ndim != 3:
+            raise ValueError("mask must be a (z, y, x) volume")
+        rois = np.ascontiguousarray(rois, np.int64)
+        if rois.ndim != 2 or rois.shape[1] != 6:
+            raise ValueError("rois must be an (n, 6) array")
+        return Context._coverage(self, mptr, mdt, mask.shape, rois.ctypes.data if rois.size else None, rois.shape[0],
+                                 round_ends, MEM_HOST)
 
     def bag_image_dense_stream(self, image, mask, sigmas, size, edges, gen_mask=None,
                                spacing=(1.0, 1.0, 1.0), values="frequencies", block_mb=0):

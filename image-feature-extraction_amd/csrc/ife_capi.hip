@@ -31,6 +31,7 @@
 #include "bspline_kernels.hpp"
 #include "region_kernels.hpp"
 #include "sampling_kernels.hpp"
+#include "coverage_kernels.hpp"
 #define IFE_IIR_NS iir_exact
 #define IFE_IIR_FMA 0
 #include "iir_kernels.inc"
@@ -1615,4 +1616,5 @@ int ife_reset_kernel_times(ife_ctx *ctx) {
 #include "labels_capi.inc"  // shares the dense centres, budget and x / y passes
 #include "region_capi.inc"
 #include "sampling_capi.inc"  // shares the dense geometry and the scans
+#include "coverage_capi.inc"  // shares the sort, the scans and the overlap check
 #include "multi_capi.inc"

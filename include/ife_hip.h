@@ -1046,6 +1046,65 @@ int ife_random_rois(ife_ctx *ctx, const void *mask, int mask_dtype, const ife_vo
 int ife_extract_rois(ife_ctx *ctx, const void *src, int elem_bytes, const ife_volume_desc *vol, const int64_t *rois,
                      int64_t n_rois, void *dst, int mem);
 
+/* ---- census and coverage: the two questions of tools/ImageBrowser.cxx ---------------------------- *
+ *
+ * Which values occur in a volume and how often (its `s` command, :165-186), and how many random
+ * boxes it takes to cover the region between two thresholds (its `r` command, :24-100).  Integers
+ * only; results are exact.  One device, the context's stream; every call blocks.
+ *
+ * ife_value_census_f32: the distinct values of values[0 .. n) in ascending order in uniq, and in
+ * counts how often each occurs: the std::set<float> of :165-168 and the DenseHistogram over its
+ * values of :169-173, whose bin i = (uniq[i-1], uniq[i]] counts the elements equal to uniq[i] and
+ * whose trailing bin (uniq[last], inf) is always 0 and is not written.  Stated on bit patterns, so
+ * that no compare's denormal mode matters:
+ *   NaN       (bits & 0x7fffffff) > 0x7f800000.  NaNs are left out and counted in *n_nan (the
+ *             reference's set has no defined behaviour there: a departure)
+ *   zeros     -0 and +0 are one value, reported as +0.0 (the reference reports whichever comes first
+ *             in raster order: a departure)
+ *   others    two elements are the same value iff their bits are equal; uniq ascends in float
+ *             order; denormals are values of their own; -inf and +inf are ordinary values
+ * uniq and counts (capacity entries each) follow mem; n_unique and n_nan are HOST pointers.
+ * capacity == 0 with uniq == counts == NULL is legal and gives the two counts alone.  Where
+ * *n_unique > capacity the call writes n_unique and n_nan, returns IFE_E_ARG with a message that
+ * names both numbers and writes nothing else.  Workspace of the context: a sorted copy and the
+ * sort's partner, 4 bytes per element each, and one count per 256 elements.  IFE_E_ARG also: a null
+ * pointer, n <= 0, a negative capacity, a DEVICE pointer not aligned to its element.  IFE_E_SIZE:
+ * n > 2^32-1; the sort underneath takes 2^31-1 elements and anything beyond is refused likewise.
+ *
+ * ife_threshold_mask: mask[i] = 1 where low <= image[i] <= high, else 0, both ends inclusive:
+ * itk::BinaryThresholdImageFilter with inside 1 and outside 0, as :35-42 sets it.  NaN elements give
+ * 0; -0 equals +0; the decision is taken on the order-preserving integer image of the bits, so
+ * denormal bounds and values compare as IEEE 754 says whatever the kernel's denormal mode.  image
+ * and mask follow mem; count is a HOST pointer, may be NULL, and receives the number of ones
+ * (regionSize, :61-66).  IFE_E_ARG: low > high (ITK throws there), a NaN bound, a null image or
+ * mask, a DEVICE image not aligned to its element, DEVICE image and mask ranges that overlap.
+ * IFE_E_SIZE: n <= 0 or n > 2^40.
+ *
+ * ife_roi_coverage: with V_r the union of the boxes k < round_ends[r],
+ *   visited[r]   = |V_r|
+ *   hits[r]      = |V_r and {mask != 0}|
+ *   *region_size = |{mask != 0}|
+ * the three numbers of every line :72-99 prints; the rounds are cumulative.  The volume is dense,
+ * x fastest, with at most 2^32-1 voxels (IFE_E_SIZE beyond).  mask_dtype is IFE_U8 or IFE_U16 and
+ * foreground is != 0 (a uint16 of 256 is foreground).  rois = [n_rois][6] {x0, y0, z0, sx, sy, sz};
+ * the boxes may differ in size.  mask and rois follow mem.  round_ends is a HOST array of n_rounds
+ * entries, 1 <= n_rounds <= 64, non-decreasing, 0 <= round_ends[r] <= n_rois.  visited and hits
+ * (HOST, n_rounds entries each) and region_size (HOST, may be NULL) receive the counts.  n_rois ==
+ * 0 (rois may be NULL then) or a round end of 0 gives zeros.  A box with a size below 1 or that
+ * leaves the volume is IFE_E_ARG with nothing written; DEVICE boxes are checked on the device
+ * before anything is painted.  IFE_E_ARG also: a decreasing round_ends, an end beyond n_rois,
+ * n_rounds outside 1 .. 64, a null pointer, a DEVICE pointer not aligned to its element.
+ * Workspace of the context: two planes of one bit per voxel. */
+int ife_value_census_f32(ife_ctx *ctx, const float *values, int64_t n, float *uniq, uint32_t *counts,
+                         int64_t capacity, int64_t *n_unique, int64_t *n_nan, int mem);
+
+int ife_threshold_mask(ife_ctx *ctx, const float *image, int64_t n, float low, float high, uint8_t *mask,
+                       int64_t *count, int mem);
+
+int ife_roi_coverage(ife_ctx *ctx, const void *mask, int mask_dtype, const ife_volume_desc *vol, const int64_t *rois,
+                     int64_t n_rois, const int64_t *round_ends, int n_rounds, int64_t *visited, int64_t *hits,
+                     int64_t *region_size, int mem);
+
 /* ---- measurement ------------------------------------------------------------------- */
 
 #define IFE_MAX_KERNEL_KINDS 24
