@@ -35,6 +35,10 @@ OPT_DIFFERENTIAL = 13  # 1: the composite calls take their features from the jet
 INTERP_LINEAR, INTERP_NEAREST = 0, 1  # ife_interp: interpolation of ife_resample
 BSPLINE_MAX_ORDER = 5  # ife_bspline_coefficients / ife_resample_bspline: orders 0 .. 5
 BAG_COUNTS, BAG_FREQUENCIES = 0, 1  # ife_bag_values: what the dense bag stream delivers
+SS_LAPLACIAN, SS_TUBE, SS_PLATE, SS_BLOB = 0, 1, 2, 3  # ife_scale_measure_kind: measures of ife_scale_select
+SS_MAX_MEASURES = 4  # IFE_SS_MAX_MEASURES
+SS_MAX_SIGMAS = 255  # scale index 255 says "no scale"
+SS_KIND_NAMES = ("laplacian", "tube", "plate", "blob")
 Z_STATE_BYTES = 32   # IFE_Z_STATE_BYTES: one state record of the slab Z pass, per line and job
 Z_OVERLAP_LO, Z_OVERLAP_HI = 3, 4  # IFE_Z_OVERLAP_*: neighbour planes around a slab's input
 NUM_FEATURES = 8
@@ -77,6 +81,7 @@ EXPORTS = (
     "ife_device_alloc", "ife_device_upload", "ife_device_free",
     "ife_sample_positions", "ife_random_rois", "ife_extract_rois",
     "ife_value_census_f32", "ife_threshold_mask", "ife_roi_coverage",
+    "ife_scale_select",
 )
 
 
@@ -87,6 +92,20 @@ class VolumeDesc(C.Structure):
 
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("total_ms", C.c_double)]
+
+
+class ScaleMeasure(C.Structure):
+    """ife_scale_measure: kind SS_*, polarity +1 (bright) or -1 (dark), gamma of the scale
+    normalisation, and alpha, beta, c of the three Frangi kinds (SS_LAPLACIAN ignores them)."""
+    _fields_ = [("kind", C.c_int32), ("polarity", C.c_int32), ("gamma", C.c_float), ("alpha", C.c_float),
+                ("beta", C.c_float), ("c", C.c_float)]
+
+    def __init__(self, kind=SS_LAPLACIAN, polarity=1, gamma=1.0, alpha=0.5, beta=0.5, c=1.0):
+        if isinstance(kind, str):
+            if kind not in SS_KIND_NAMES:
+                raise ValueError("kind must be one of %s" % (SS_KIND_NAMES,))
+            kind = SS_KIND_NAMES.index(kind)
+        super().__init__(int(kind), int(polarity), float(gamma), float(alpha), float(beta), float(c))
 
 
 class IfeError(RuntimeError):
@@ -247,6 +266,8 @@ def load_library():
     lib.ife_threshold_mask.argtypes = [vp, vp, i64, C.c_float, C.c_float, vp, C.POINTER(i64), i32]
     lib.ife_roi_coverage.argtypes = [vp, vp, i32, vd, vp, i64, C.POINTER(i64), i32, C.POINTER(i64), C.POINTER(i64),
                                      C.POINTER(i64), i32]
+    lib.ife_scale_select.argtypes = [vp, vp, i32, vp, i32, vd, C.POINTER(C.c_float), i32, C.POINTER(ScaleMeasure), i32,
+                                     vp, vp, i32]
     _lib = lib
     return lib
 
@@ -388,6 +409,32 @@ def _threshold_args(low, high):
     if low > high:
         raise ValueError("Lower threshold cannot be greater than upper threshold.")
     return C.c_float(float(low)), C.c_float(float(high))
+
+
+def _scale_measures_arg(measures, n_sigmas):
+    """The measures of ife_scale_select as a ctypes array, refused as the library refuses them."""
+    measures = list(measures)
+    if not 1 <= len(measures) <= SS_MAX_MEASURES:
+        raise ValueError("n_measures must lie in 1 .. %d" % SS_MAX_MEASURES)
+    if n_sigmas > SS_MAX_SIGMAS:
+        raise ValueError("n_sigmas must be at most %d" % SS_MAX_SIGMAS)
+    arr = (ScaleMeasure * len(measures))()
+    for k, m in enumerate(measures):
+        if not isinstance(m, ScaleMeasure):
+            m = ScaleMeasure(**m) if isinstance(m, dict) else ScaleMeasure(*m)
+        if m.kind not in (SS_LAPLACIAN, SS_TUBE, SS_PLATE, SS_BLOB):
+            raise ValueError("measures[%d]: kind is not a measure kind" % k)
+        if m.polarity not in (1, -1):
+            raise ValueError("measures[%d]: polarity must be +1 or -1" % k)
+        if not (m.gamma >= 0 and np.isfinite(m.gamma)):
+            raise ValueError("measures[%d]: gamma must be finite and not negative" % k)
+        if m.kind != SS_LAPLACIAN:
+            for name in ("alpha", "beta", "c"):
+                v = getattr(m, name)
+                if not (v > 0 and np.isfinite(v)):
+                    raise ValueError("measures[%d]: %s must be positive and finite" % (k, name))
+        arr[k] = m
+    return arr
 
 
 def _round_ends_arg(round_ends, n_rois):
@@ -1445,6 +1492,36 @@ class Context:
             raise ValueError("rois must be an (n, 6) array")
         return Context._coverage(self, mptr, mdt, mask.shape, rois.ctypes.data if rois.size else None, rois.shape[0],
                                  round_ends, MEM_HOST)
+
+    def scale_select_device(self, image_ptr, image_dtype, mask_ptr, mask_dtype, shape_zyx, spacing, sigmas,
+                            measures, response_ptr, index_ptr=None):
+        """Enqueues on the context's stream and waits; response_ptr: [n_measures][nvox] float32,
+        index_ptr: the same in uint8 or None, both in device memory (ife_scale_select)."""
+        d = _desc(shape_zyx, spacing)
+        sig = _sigma_arg(sigmas)
+        ms = _scale_measures_arg(measures, len(sigmas))
+        self._chk(self._lib.ife_scale_select(
+            self._h, C.c_void_p(image_ptr or 0), image_dtype, C.c_void_p(mask_ptr or 0), mask_dtype, C.byref(d), sig,
+            len(sigmas), ms, len(ms), C.c_void_p(response_ptr or 0), C.c_void_p(index_ptr or 0), MEM_DEVICE))
+
+    def scale_select(self, image, mask, sigmas, measures, spacing=(1.0, 1.0, 1.0), want_index=True):
+        """The maximum over the scales of every measure (ScaleMeasure) and the index of the scale
+        that reached it: (response (M, nz, ny, nx) float32, index (M, nz, ny, nx) uint8 or None).
+        Index 255 with response 0: no scale had a positive response.  The features are those of
+        emphysema_features, with OPT_DIFFERENTIAL at 1 those of differential_features."""
+        image, idt = _image_arg(image)
+        if image.ndim != 3:
+            raise ValueError("image must be a (z, y, x) volume")
+        mask, mdt, mptr = _mask_arg(mask)
+        ms = _scale_measures_arg(measures, len(sigmas))
+        d = _desc(image.shape, spacing)
+        sig = _sigma_arg(sigmas)
+        response = np.empty((len(ms),) + image.shape, np.float32)
+        index = np.empty((len(ms),) + image.shape, np.uint8) if want_index else None
+        self._chk(self._lib.ife_scale_select(
+            self._h, image.ctypes.data, idt, mptr, mdt, C.byref(d), sig, len(sigmas), ms, len(ms),
+            response.ctypes.data, index.ctypes.data if want_index else None, MEM_HOST))
+        return response, index
 
     def bag_image_dense_stream(self, image, mask, sigmas, size, edges, gen_mask=None,
                                spacing=(1.0, 1.0, 1.0), values="frequencies", block_mb=0):

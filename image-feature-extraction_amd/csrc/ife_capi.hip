@@ -32,6 +32,7 @@
 #include "region_kernels.hpp"
 #include "sampling_kernels.hpp"
 #include "coverage_kernels.hpp"
+#include "scale_select_kernels.hpp"
 #define IFE_IIR_NS iir_exact
 #define IFE_IIR_FMA 0
 #include "iir_kernels.inc"
@@ -197,6 +198,7 @@ struct ife_ctx {
     int64_t n_rois = 0, ld = 0;
   } ds;
   DevBuf dj_ws;  // differential convolution: the field slots of one scale (diff_capi.inc)
+  DevBuf ss_ws;  // scale selection: one planar scale of features (scale_select_capi.inc)
   // streaming form of the scale loop (ife_emphysema_features_begin / _fetch / _end)
   DevBuf sc_out;                     // all scales, device resident
   std::vector<hipEvent_t> sc_done;   // one per scale: its feature launch has finished
@@ -1607,6 +1609,7 @@ int ife_reset_kernel_times(ife_ctx *ctx) {
 
 #include "diff_capi.inc"    // the jet of one scale
 #include "scales_capi.inc"  // the scale loop over both paths, before its users: the sample and dense calls
+#include "scale_select_capi.inc"  // a fourth sink of the scale loop
 #include "deflate_capi.inc"  // reads the scale stream
 #include "stats_capi.inc"
 #include "distance_capi.inc"

@@ -1105,6 +1105,56 @@ int ife_roi_coverage(ife_ctx *ctx, const void *mask, int mask_dtype, const ife_v
                      int64_t n_rois, const int64_t *round_ends, int n_rounds, int64_t *visited, int64_t *hits,
                      int64_t *region_size, int mem);
 
+/* ---- scale selection: the maximum over scales of a gamma-normalised measure -------------------- *
+ *
+ * Ours: the reference computes its features per scale and never reduces over scales (SURVEY.md
+ * section 0.6).  For every voxel and every requested measure the call gives the largest response
+ * over the scales and the index of the scale that reached it, without ever holding more than one
+ * scale of features: 5 bytes per voxel and measure leave the device instead of 32 per voxel and
+ * scale.
+ *
+ * Per voxel and scale s:
+ *   e1, e2, e3   feature components 2, 3, 4 (|e1| >= |e2| >= |e3|) and L component 5, exactly what
+ *                ife_emphysema_features gives for sigmas[s] -- with IFE_OPT_DIFFERENTIAL at 1, what
+ *                ife_differential_features gives
+ *   w_s          (float)pow((double)sigmas[s], 2 * (double)gamma), formed on the host
+ *   a1 = w_s*e3, a2 = w_s*e2, a3 = w_s*e1, in float: |a1| <= |a2| <= |a3|
+ *   polarity     +1: bright structures (negative curvature), -1: dark ones; a_k "has the sign"
+ *                when -polarity * a_k > 0
+ *   Ra2 = a2^2 / a3^2;  Rb2 = a1^2 / |a2*a3|, 0 where a2 == 0;  S2 = a1^2 + a2^2 + a3^2
+ *   A = exp(-Ra2 / (2 alpha^2));  B = exp(-Rb2 / (2 beta^2));  C = 1 - exp(-S2 / (2 c^2))
+ *   in float arithmetic with expf; the three reciprocals 1/(2 alpha^2), 1/(2 beta^2), 1/(2 c^2)
+ *   are formed on the host in double and rounded to float.
+ * The response r of a measure kind:
+ *   IFE_SS_LAPLACIAN   -polarity * (w_s * L): one float product, exact (Lindeberg's blob detector)
+ *   IFE_SS_TUBE        (1 - A) * B * C        where a2 and a3 have the sign, else 0
+ *   IFE_SS_PLATE       A * B * C              where a3 has the sign, else 0
+ *   IFE_SS_BLOB        (1 - A) * (1 - B) * C  where a1, a2 and a3 have the sign, else 0
+ * The fold over the scales, in the order given: best = 0 and index = 255; scale s replaces them
+ * only when r > best, strictly, so the first of equal scales wins and a NaN never does.  A voxel
+ * outside the mask has zero features, hence (0, 255).
+ *
+ * measures and sigmas are HOST arrays; image, mask, response and scale_index follow mem (HOST or
+ * DEVICE; the call blocks in both).  response is [n_measures][nvox] float, scale_index the same
+ * in uint8 or NULL, which changes nothing in response.  DEVICE: response at any float alignment,
+ * scale_index at any byte.  Volume, sigmas, image and mask as for ife_emphysema_features.
+ * IFE_E_ARG with a message that names the argument: n_measures outside 1 .. IFE_SS_MAX_MEASURES;
+ * n_sigmas > 255; an unknown kind; a polarity other than +1 or -1; gamma negative or not finite;
+ * alpha, beta or c not positive and finite for the three Frangi kinds (IFE_SS_LAPLACIAN ignores
+ * them).  A refused call writes nothing and leaves the context usable.  Workspace of the
+ * context: that of the feature call and one planar scale of features, 32 bytes per voxel. */
+typedef enum { IFE_SS_LAPLACIAN = 0, IFE_SS_TUBE = 1, IFE_SS_PLATE = 2, IFE_SS_BLOB = 3 } ife_scale_measure_kind;
+#define IFE_SS_MAX_MEASURES 4
+typedef struct ife_scale_measure {
+  int32_t kind, polarity;
+  float gamma, alpha, beta, c;
+} ife_scale_measure;
+
+int ife_scale_select(ife_ctx *ctx, const void *image, int image_dtype, const void *mask, int mask_dtype,
+                     const ife_volume_desc *vol, const float *sigmas, int n_sigmas,
+                     const ife_scale_measure *measures, int n_measures, float *response, uint8_t *scale_index,
+                     int mem);
+
 /* ---- measurement ------------------------------------------------------------------- */
 
 #define IFE_MAX_KERNEL_KINDS 24
